@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- timesteps/s of the Cahn-Hilliard solver loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one iteration of chsimpy/solver.py:165-249 (pointwise chemical
 potential -> 2-D DCT-II -> spectral update -> inverse DCT -> energy/statistics
@@ -13,7 +13,10 @@ RCCL) advances its own independent member of a Monte-Carlo ensemble (chsimpy/exp
 per GPU, A0/A1 scaled per rank) -- weak scaling, no data-path collective; the only
 collective is the all_gather of the per-run energy scalars at the end.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; --full adds
+what is measured beside the headline: the other call protocol, the per-kernel profile and roofline, the extra
+figures of DESIGN.md section 7 and the single-core CPU baseline.  --dump-outputs DIR writes what the timed call
+computed (dump_outputs).
 """
 import argparse
 import json
@@ -42,10 +45,14 @@ def parse():
     ap.add_argument('--grid', type=int, default=4096, help='N (default: BASELINE.json configs[2])')
     ap.add_argument('--dtype', default='float64')
     ap.add_argument('--engine', default='auto')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: the other call protocol, '
+                    'the per-kernel profile and roofline, the extra figures and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the timed call computed as DIR/<name>.npy '
+                    '(float64: the record rows and the final field, see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-steps', type=int, default=0, help='0 = size the CPU sample automatically')
-    ap.add_argument('--profile-steps', type=int, default=20)
-    ap.add_argument('--no-extras', action='store_true', help='skip the two extra figures a default --gpus 1 line carries under '
+    ap.add_argument('--profile-steps', type=int, default=20, help='steps of the per-kernel profile of --full')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the two extra figures a --gpus 1 line carries under '
                     'config (full_call_5000_ms_per_step, cfg3_n8192_f32_adaptive_steps_per_s): A/B scripts')
     ap.add_argument('--energy-stop', action='store_true', help='full_sim=False (the reference default: stop at the E2 maximum); not the headline workload')
     ap.add_argument('--continue-loop', action='store_true', help='the timed call continues the device loop of the warm-up call '
@@ -87,6 +94,59 @@ SLOT_TRANSFERS = {
     'fast': {'k_row_fwd (prologue)': 2, 'k_col': 4, 'k_row_inv (fused)': 4},
     'direct': {},
 }
+
+
+def roofline(eng, N, esz, ms_per_step, profile_steps):
+    """--full: the dominant kernel against the HBM peak, from `profile_steps` steps timed kernel by kernel with HIP
+    events on the engine's stream."""
+    bytes_step = algorithmic_bytes_per_step(N, esz)
+    ms, calls = eng.profile_steps(profile_steps)
+    names = eng.kernel_names()
+    per = {names[i]: ms[i] / calls[i] for i in range(len(names)) if names[i] and calls[i] > 0}
+    tot = {names[i]: ms[i] for i in range(len(names)) if names[i] and calls[i] > 0}
+    dom = max(tot, key=tot.get)  # dominant = most device time over the profiled steps (not the once-per-call prologue)
+    transfers = SLOT_TRANSFERS.get(eng.engine, {}).get(dom)
+    if transfers is None:
+        # kernels outside the 8-transfer model: price them with the whole-step figure
+        dom_bytes = None
+        achieved = bytes_step / (sum(per.values()) * 1e-3) / 1e9
+    else:
+        dom_bytes = transfers * N * N * esz
+        achieved = dom_bytes / (per[dom] * 1e-3) / 1e9
+    traffic = None
+    tf = os.path.join(ROOT, 'profiles', 'traffic.json')
+    if os.path.exists(tf):
+        try:
+            traffic = json.load(open(tf)).get(f'{eng.engine}:{dom}:N{N}' + (':f32' if esz == 4 else ''))
+        except Exception:
+            traffic = None
+    return {'bound': 'hbm', 'kernel': dom, 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS,
+            'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
+            'algorithmic_bytes_per_launch': dom_bytes,
+            'avg_launch_ms': round(per[dom], 5),
+            'kernel_ms': {k: round(v, 5) for k, v in per.items()},
+            'whole_step': {'algorithmic_bytes': bytes_step,
+                           'achieved': round(bytes_step / (ms_per_step * 1e-3) / 1e9, 1),
+                           'frac': round(bytes_step / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
+
+
+DUMP_ROWS = 1 << 16      # record rows kept by dump_outputs: the last 65536 (4.5 MiB)
+DUMP_POINTS = 1 << 21    # points of the field kept by dump_outputs (16 MiB)
+
+
+def dump_outputs(d, rows, U):
+    """What the timed call hands its caller, as float64 .npy files under `d` (at most 21 MiB in all):
+    * timedata.npy -- the record rows of the timed call (solve_or_resume's timedata, column order timedata.py:9),
+      the last DUMP_ROWS of them;
+    * U.npy -- the field after the last timed step (solver.py:251), flattened: the whole field up to DUMP_POINTS
+      points, else the points at the DUMP_POINTS sorted flat indices PCG64(0) draws without replacement (the same
+      sample for every run at the same N)."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'timedata.npy'), np.ascontiguousarray(rows[-DUMP_ROWS:], dtype=np.float64))
+    flat = np.ascontiguousarray(U, dtype=np.float64).ravel()
+    if flat.size > DUMP_POINTS:
+        flat = flat[np.sort(np.random.Generator(np.random.PCG64(0)).choice(flat.size, DUMP_POINTS, replace=False))]
+    np.save(os.path.join(d, 'U.npy'), flat)
 
 
 def time_repetitions(run_once, warmups=1, repetitions=3):
@@ -200,7 +260,8 @@ def ensemble_baseline(a):
     # the whole pool.map (set-up and prepare() included, amortised over only `steps` timesteps) is reported beside it.
     timed = solve_s[1:]                                   # (the first repetition is the warm-up)
     member_mean = sum(sum(r) for r in timed) / (len(timed) * P)
-    cpu = {'value': P * steps / member_mean, 'best': P * steps / min(max(r) for r in timed), 'unit': 'timesteps/s (aggregate)',
+    # best: the repetition with the lowest member mean, the same quantity `value` averages over all repetitions
+    cpu = {'value': P * steps / member_mean, 'best': P * steps / min(sum(r) / P for r in timed), 'unit': 'timesteps/s (aggregate)',
            'cores': P, 'cores_cap': 16 if not a.ens_procs else None, 'kind': 'port', 'per_member_steps_per_s': steps / member_mean,
            'wall_incl_setup_steps_per_s': P * steps / mean,
            'comparator_note': f'{P} processes (the cores a one-GPU job is meant to use, capped at 16; the reference sizes its pool '
@@ -373,7 +434,7 @@ def main():
     # solve_or_resume call of the reference, literally: it enters through hat_U = dctn(U) (solver.py:159), runs
     # `steps` complete timesteps and leaves U in HBM (solver.py:251).  --continue-loop times the engine's own
     # mode for the chunks of one run instead (hat_U carried across the call boundary, last call of the run);
-    # its figure is reported beside the headline either way (config.other_protocol_ms_per_step).
+    # with --full the other protocol's figure is reported beside the headline (config.other_protocol_ms_per_step).
     literal = dict(rederive_hat=True, last_call=False)
     carried = dict(rederive_hat=False, last_call=True)
     sync()
@@ -384,9 +445,11 @@ def main():
     assert nocheck or (rows.shape[0] == a.steps and rc == 0), (rows.shape, rc)
     dt = t1 - t0
     dev_ms = eng.last_step_ms()
-    # the other protocol, right behind the timed region (same clocks), for the record
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rows, eng.get_U())
+    # --full: the other protocol, right behind the timed region (same clocks), for the record
     other_ms = None
-    if world == 1 and not a.energy_stop:   # (with the stop rule armed the run must still be alive for the profile leg below)
+    if a.full and world == 1 and not a.energy_stop:   # (with the stop rule armed the run must still be alive for the profile leg below)
         if not a.continue_loop:
             eng.step_n(a.steps)   # a completed call whose loop the continuing call can take up (a literal call leaves none)
         torch.cuda.synchronize()
@@ -412,36 +475,6 @@ def main():
     if rank == 0:
         value = world * a.steps / dt
         ms_per_step = dt * 1e3 / a.steps
-        bytes_step = algorithmic_bytes_per_step(N, esz)
-        # dominant kernel, HIP events on the engine's stream
-        ms, calls = eng.profile_steps(a.profile_steps)
-        names = eng.kernel_names()
-        per = {names[i]: ms[i] / calls[i] for i in range(len(names)) if names[i] and calls[i] > 0}
-        tot = {names[i]: ms[i] for i in range(len(names)) if names[i] and calls[i] > 0}
-        dom = max(tot, key=tot.get)  # dominant = most device time over the profiled steps (not the once-per-call prologue)
-        transfers = SLOT_TRANSFERS.get(eng.engine, {}).get(dom)
-        if transfers is None:
-            # kernels outside the 8-transfer model: price them with the whole-step figure
-            dom_bytes = None
-            achieved = bytes_step / (sum(per.values()) * 1e-3) / 1e9
-        else:
-            dom_bytes = transfers * N * N * esz
-            achieved = dom_bytes / (per[dom] * 1e-3) / 1e9
-        traffic = None
-        tf = os.path.join(ROOT, 'profiles', 'traffic.json')
-        if os.path.exists(tf):
-            try:
-                traffic = json.load(open(tf)).get(f'{eng.engine}:{dom}:N{N}' + (':f32' if esz == 4 else ''))
-            except Exception:
-                traffic = None
-        roofline = {'bound': 'hbm', 'kernel': dom, 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS,
-                    'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
-                    'algorithmic_bytes_per_launch': dom_bytes,
-                    'avg_launch_ms': round(per[dom], 5),
-                    'kernel_ms': {k: round(v, 5) for k, v in per.items()},
-                    'whole_step': {'algorithmic_bytes': bytes_step,
-                                   'achieved': round(bytes_step / (ms_per_step * 1e-3) / 1e9, 1),
-                                   'frac': round(bytes_step / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
         out = {
             'metric': metric_name(N, a.dtype),
             'value': round(value, 3), 'unit': 'timesteps/s', 'n_gpus': world, 'steps': a.steps,
@@ -458,21 +491,22 @@ def main():
                        'untimed_steps_before_timed_region': max(a.warmup, PREWARM),
                        'call_entry': 'continues the device loop of the warm-up call (hat_U resident, last call of the run)'
                                      if a.continue_loop else
-                                     'one literal solve_or_resume call: hat_U = dctn(U) recomputed on entry (solver.py:159), U stored at the end (251)',
-                       'other_protocol': 'literal solve_or_resume call' if a.continue_loop else 'continuing the device loop (hat_U carried)',
-                       'other_protocol_ms_per_step': None if other_ms is None else round(other_ms, 5)},
-            'roofline': roofline,
+                                     'one literal solve_or_resume call: hat_U = dctn(U) recomputed on entry (solver.py:159), U stored at the end (251)'},
             'energies_last_step': energies,
         }
-        if world == 1 and not a.no_extras and N == 4096 and esz == 8 and not a.energy_stop and eng.engine == 'fast':
-            try:
-                out['config'].update(extra_figures(a, eng, torch, device))
-            except Exception as e:   # (the extra figures must never cost the line itself)
-                out['config']['extras_error'] = f'{type(e).__name__}: {e}'[:300]
-        if not a.no_cpu_baseline and world == 1:
-            out['cpu_baseline'] = cpu_baseline(N, a.cpu_steps)
-        elif world == 1:
-            out['cpu_baseline'] = None
+        if a.full:
+            out['config']['other_protocol'] = 'literal solve_or_resume call' if a.continue_loop else 'continuing the device loop (hat_U carried)'
+            out['config']['other_protocol_ms_per_step'] = None if other_ms is None else round(other_ms, 5)
+            out['roofline'] = roofline(eng, N, esz, ms_per_step, a.profile_steps)
+            if world == 1 and not a.no_extras and N == 4096 and esz == 8 and not a.energy_stop and eng.engine == 'fast':
+                try:
+                    out['config'].update(extra_figures(a, eng, torch, device))
+                except Exception as e:   # (the extra figures must never cost the line itself)
+                    out['config']['extras_error'] = f'{type(e).__name__}: {e}'[:300]
+            if not a.no_cpu_baseline and world == 1:
+                out['cpu_baseline'] = cpu_baseline(N, a.cpu_steps)
+            elif world == 1:
+                out['cpu_baseline'] = None
     s.close()
     if dist is not None:
         dist.barrier()

@@ -5,7 +5,7 @@
 #   is never overwritten (an interrupted A/B cannot leave a variant behind as the product).
 rounds=${1:-2}
 shift
-args=${@:---steps 300 --warmup 300}
+args="--full ${@:---steps 300 --warmup 300}"   # (--full: the per-kernel figures printed below)
 mkdir -p gpurun_out
 : > gpurun_out/ab.log
 for r in $(seq $rounds); do

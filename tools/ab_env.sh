@@ -5,7 +5,7 @@ rounds=$1; shift
 sets=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do sets+=("$1"); shift; done
 shift
-args=${@:---steps 300 --warmup 300}
+args="--full ${@:---steps 300 --warmup 300}"   # (--full: the other protocol and per-kernel figures printed below)
 mkdir -p gpurun_out
 : > gpurun_out/ab_env.log
 for r in $(seq $rounds); do

@@ -4,7 +4,7 @@
 tag=${1:-rXX}
 o=gpurun_out
 mkdir -p $o
-run() { name=$1; shift; timeout -k 10 400 python bench.py "$@" > $o/${tag}_$name.json 2> $o/${tag}_$name.err || echo "$name failed"; }
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > $o/${tag}_$name.json 2> $o/${tag}_$name.err || echo "$name failed"; }
 run bench                                   # headline: N=4096 fp64, 300 + 5000 steps, with the CPU baseline
 run bench_driver --steps 20 --warmup 5 --no-cpu-baseline   # the driver's invocation (literal solve_or_resume call)
 run bench_driver_continue --steps 20 --warmup 5 --no-cpu-baseline --continue-loop
