@@ -10,6 +10,7 @@ from .solution import Solution
 from .timedata import TimeData
 from .solver import Solver
 from .simulator import Simulator
+from .batch import BatchSolver
 from . import utils, mport
 
-__all__ = ['Parameters', 'Solution', 'TimeData', 'Solver', 'Simulator', 'utils', 'mport', '__version__']
+__all__ = ['Parameters', 'Solution', 'TimeData', 'Solver', 'Simulator', 'BatchSolver', 'utils', 'mport', '__version__']

@@ -32,7 +32,12 @@ SYMBOLS = (
     'chs_get_state', 'chs_set_state', 'chs_set_jitter_noise', 'chs_set_jitter_pcg64', 'chs_dctn', 'chs_get_mu', 'chs_test_math',
     'chs_engine', 'chs_kernel_name', 'chs_profile_steps', 'chs_last_step_ms',
     'chs_last_error', 'chs_version',
+    'chs_batch_create', 'chs_batch_destroy', 'chs_batch_set_U', 'chs_batch_init_U_pcg64', 'chs_batch_get_U',
+    'chs_batch_prepare', 'chs_batch_step_n', 'chs_batch_get_state', 'chs_batch_set_state',
 )
+
+# the N a batch takes (include/chs_hip.h: chs_batch_create)
+BATCH_SIZES = (128, 256, 512, 1024, 2048)
 
 
 class chs_consts(C.Structure):
@@ -128,6 +133,16 @@ def load():
     lib.chs_last_error.restype = C.c_char_p
     lib.chs_version.restype = C.c_char_p
     lib.chs_pool_clear.argtypes = []
+    vp, u64p, i64p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+    lib.chs_batch_create.argtypes = [C.POINTER(chs_consts), C.c_int32, dp, C.POINTER(C.c_void_p)]
+    lib.chs_batch_destroy.argtypes = [vp]
+    lib.chs_batch_set_U.argtypes = [vp, C.c_int32, dp]
+    lib.chs_batch_init_U_pcg64.argtypes = [vp, C.c_int32, C.c_double, C.c_double, u64p, u64p]
+    lib.chs_batch_get_U.argtypes = [vp, C.c_int32, dp]
+    lib.chs_batch_prepare.argtypes = [vp, dp]
+    lib.chs_batch_step_n.argtypes = [vp, i64p, C.c_int32, dp, i64p, C.POINTER(C.c_int32)]
+    lib.chs_batch_get_state.argtypes = [vp, C.c_int32, C.POINTER(chs_state)]
+    lib.chs_batch_set_state.argtypes = [vp, C.c_int32, C.POINTER(chs_state)]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -293,3 +308,79 @@ class Engine:
 
     def last_step_ms(self):
         return float(self.lib.chs_last_step_ms(self._h))
+
+
+def _u128_pair(x):
+    m64 = (1 << 64) - 1
+    return (C.c_uint64 * 2)((int(x) >> 64) & m64, int(x) & m64)
+
+
+class Batch:
+    """B device-resident simulations of one N, dtype and device advanced together (an opaque ``chs_batch``):
+    every step kernel is launched once for all members.  Member-wise the methods are those of `Engine`."""
+
+    def __init__(self, consts_list, lam):
+        self.lib = load()
+        self.B = len(consts_list)
+        self.N = int(consts_list[0].N) if self.B else 0
+        self._h = C.c_void_p()
+        arr = (chs_consts * max(self.B, 1))(*consts_list)
+        lam = _as_f64(lam, (self.N,))
+        self._check(self.lib.chs_batch_create(arr, self.B, _dptr(lam), C.byref(self._h)), 'chs_batch_create')
+
+    _check = Engine._check
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            self.lib.chs_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_U(self, member, U):
+        U = _as_f64(U, (self.N, self.N))
+        self._check(self.lib.chs_batch_set_U(self._h, int(member), _dptr(U)), 'chs_batch_set_U')
+
+    def init_U_pcg64(self, member, base, scale, state, inc):
+        self._check(self.lib.chs_batch_init_U_pcg64(self._h, int(member), float(base), float(scale), _u128_pair(state),
+                                                    _u128_pair(inc)), 'chs_batch_init_U_pcg64')
+
+    def get_U(self, member):
+        U = np.empty((self.N, self.N), dtype=np.float64)
+        self._check(self.lib.chs_batch_get_U(self._h, int(member), _dptr(U)), 'chs_batch_get_U')
+        return U
+
+    def prepare(self):
+        """[B, 9] step-0 records; raises like `Engine.prepare` when one of them is NaN."""
+        rows = np.empty((self.B, 9), dtype=np.float64)
+        self._check(self.lib.chs_batch_prepare(self._h, _dptr(rows)), 'chs_batch_prepare')
+        return rows
+
+    def step_n(self, nsteps):
+        """One literal call for every member: nsteps[m] iterations of member m.  Returns (list of rows[k_m, 9],
+        list of per-member rc -- CHS_OK or CHS_ENAN, the rows then end with the NaN row)."""
+        n = np.ascontiguousarray([max(int(k), 0) for k in nsteps], dtype=np.int64)
+        if n.size != self.B:
+            raise ValueError(f"nsteps needs {self.B} entries, got {n.size}")
+        mx = int(n.max()) if n.size else 0
+        rows = np.empty((self.B, max(mx, 1), 9), dtype=np.float64)
+        done = np.zeros(self.B, dtype=np.int64)
+        status = np.zeros(self.B, dtype=np.int32)
+        rc = self.lib.chs_batch_step_n(self._h, n.ctypes.data_as(C.POINTER(C.c_int64)), 0, _dptr(rows),
+                                       done.ctypes.data_as(C.POINTER(C.c_int64)),
+                                       status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc not in (CHS_OK, CHS_ENAN):
+            self._check(rc, 'chs_batch_step_n')
+        return [rows[m, :done[m]].copy() for m in range(self.B)], [int(x) for x in status]
+
+    def get_state(self, member):
+        s = chs_state()
+        self._check(self.lib.chs_batch_get_state(self._h, int(member), C.byref(s)), 'chs_batch_get_state')
+        return s
+
+    def set_state(self, member, s):
+        self._check(self.lib.chs_batch_set_state(self._h, int(member), C.byref(s)), 'chs_batch_set_state')

@@ -1,0 +1,204 @@
+"""``BatchSolver``: several ``Solver`` runs of one grid size advanced together on one device.
+
+An ensemble over (A0, A1) at the reference's default grid (N=512) leaves an MI355X mostly idle with one run at a
+time: a step is two short dependent chains of kernels.  A batch launches every step kernel once for all of its
+members (``chs_batch_*`` of ``include/chs_hip.h``), so that the members' chains overlap on the device.
+
+Member by member a ``BatchSolver`` is a ``Solver`` with ``rederive_hat=True``: same constants, start field, records,
+stop rules and quirks (the first ``solve_or_resume`` after ``prepare`` runs ``nsteps-1`` iterations; ``prepare`` does
+not reset ``delt`` / ``time_delta_sum`` / ``skip_check``), every call a literal ``solve_or_resume`` of the reference.
+Its scope: the fast engine, N in {128, 256, 512, 1024, 2048}, one dtype and device for all members, a fixed time step
+and no jitter; anything else raises ``ValueError`` before the device is touched.
+
+    bs = BatchSolver([params_0, params_1, ...])
+    bs.prepare()
+    solutions = bs.solve_or_resume()      # one Solution per member
+    bs.close()
+"""
+import numpy as np
+
+from . import _lib
+from .solver import Solver
+
+
+def scope_error(params):
+    """Why one member's parameters are outside what a batch runs (a string), or None."""
+    N = int(params.N)
+    if N not in _lib.BATCH_SIZES:
+        return f"N={N}: a batch takes N in {{{', '.join(str(n) for n in _lib.BATCH_SIZES)}}}"
+    if str(getattr(params, 'engine', 'auto')) not in ('auto', 'fast'):
+        return f"engine={params.engine!r}: a batch runs the fast engine only"
+    if str(getattr(params, 'dtype', 'float64')) not in _lib.DTYPES:
+        return f"dtype={params.dtype!r} is not supported"
+    if params.adaptive_time:
+        return "adaptive_time: a batch takes a fixed time step only"
+    if params.jitter is not None and 0.0 < params.jitter < 0.1:
+        return "jitter: a batch has no per-step noise"
+    return None
+
+
+def _key(params):
+    return (int(params.N), _lib.DTYPES[str(getattr(params, 'dtype', 'float64'))], int(getattr(params, 'device', 0) or 0))
+
+
+def validate(params_list):
+    """Raise ValueError unless the members can share one batch (host-side checks only)."""
+    if len(params_list) < 1:
+        raise ValueError("a batch needs at least one member")
+    for i, p in enumerate(params_list):
+        why = scope_error(p)
+        if why:
+            raise ValueError(f"member {i}: {why}")
+    k0 = _key(params_list[0])
+    for i, p in enumerate(params_list):
+        if _key(p) != k0:
+            raise ValueError(f"member {i}: (N, dtype, device) = {_key(p)} differs from member 0's {k0}")
+
+
+class _Member:
+    """What a member's ``Solver`` calls on its engine, answered by the batch."""
+
+    def __init__(self, batch, m):
+        self._b, self._m = batch, m
+
+    def get_state(self):
+        return self._b.get_state(self._m)
+
+    def set_state(self, s):
+        self._b.set_state(self._m, s)
+
+    def get_U(self):
+        return self._b.get_U(self._m)
+
+    def set_U(self, U):
+        self._b.set_U(self._m, U)
+
+    def close(self):
+        pass  # (the batch owns the device state)
+
+
+class BatchSolver:
+    def __init__(self, params_list, U_init=None):
+        params_list = list(params_list)
+        validate(params_list)
+        B = len(params_list)
+        if U_init is None or (isinstance(U_init, np.ndarray) and U_init.ndim == 2):
+            inits = [U_init] * B
+        else:
+            inits = list(U_init)
+            if len(inits) != B:
+                raise ValueError(f"U_init: {len(inits)} fields for {B} members")
+        self.solvers = [Solver(p, u) for p, u in zip(params_list, inits)]
+        lam0 = self.solvers[0].solution.lam
+        for i, s in enumerate(self.solvers):
+            if not np.array_equal(s.solution.lam, lam0):
+                raise ValueError(f"member {i}: eigenvalue table differs from member 0's")
+        self._batch = None
+        self._prepared = False
+        self.member_errors = {}
+
+    @property
+    def solutions(self):
+        return [s.solution for s in self.solvers]
+
+    def __len__(self):
+        return len(self.solvers)
+
+    def _get_batch(self):
+        if self._batch is None:
+            self._batch = _lib.Batch([s._consts() for s in self.solvers], self.solvers[0].solution.lam)
+            for m, s in enumerate(self.solvers):
+                s._engine = _Member(self._batch, m)
+        return self._batch
+
+    # -- solver.py:84-135, member by member -------------------------------------------------------------------
+    def prepare(self):
+        b = self._get_batch()
+        on_device = []
+        for m, s in enumerate(self.solvers):
+            s._push_state()
+            dev = s._U_init is None and s._pcg_state0 is not None and s.device_rng
+            on_device.append(dev)
+            if dev:
+                st = s._pcg_state0['state']
+                p = s.params
+                b.init_U_pcg64(m, p.XXX, p.XXX * 0.01, st['state'], st['inc'])
+            else:
+                U = s.U_init.copy()
+                assert U.shape == (s.params.N, s.params.N)
+                b.set_U(m, U)
+        rows0 = b.prepare()
+        from .timedata import TimeData
+        for m, s in enumerate(self.solvers):
+            row = rows0[m]
+            data = TimeData()
+            data.insert(it=0, delt=row[8], E=row[1], E2=row[2], SA=0, domtime=0, Ra=row[5], L2=0, PS=row[7])
+            sol = s.solution
+            sol._bind_device_U(None if on_device[m] else s.U_init.copy(), s._engine.get_U if on_device[m] else None)
+            sol.timedata = data
+            sol.tau0 = 0.0
+            sol.t0 = 0.0
+            sol.stop_reason = 'None'
+            sol.computed_steps = 1
+            s._prepared = True
+        self._prepared = True
+
+    # -- solver.py:137-252, member by member; one device call for all ----------------------------------------
+    def solve_or_resume(self, nsteps=None):
+        """One literal solve_or_resume call of every member (``nsteps``: one count for all, a list of one per
+        member, or None = each member's ntmax).  Returns the members' Solutions.  A member whose record turns NaN
+        raises AssertionError as ``Solver`` does -- after every member's result has been taken in
+        (``member_errors`` maps the member to its error)."""
+        assert self._prepared is True
+        b = self._batch
+        B = len(self.solvers)
+        if nsteps is None or np.isscalar(nsteps):
+            per = [nsteps] * B
+        else:
+            per = list(nsteps)
+            if len(per) != B:
+                raise ValueError(f"nsteps: {len(per)} counts for {B} members")
+        counts = []
+        for m, s in enumerate(self.solvers):
+            n = per[m]
+            if n is None:
+                n = max(s.params.ntmax, 0)
+            sol = s.solution
+            if sol.__dict__.get('_U_dirty') or sol._host_edited():
+                b.set_U(m, sol.__dict__['_U'])   # solver.py:158: the field the caller assigned
+                sol.__dict__['_U_dirty'] = False
+                sol.__dict__['_U_print'] = None
+            itbegin = 1 if sol.computed_steps == 1 else 0
+            counts.append(max(int(n) - itbegin, 0))
+        rows, status = b.step_n(counts)
+        self.member_errors = {}
+        for m, s in enumerate(self.solvers):
+            try:
+                s._absorb(rows[m], status[m], counts[m])
+            except AssertionError as e:
+                self.member_errors[m] = e
+                continue
+            s.solution._bind_device_U(None, s._engine.get_U)   # downloaded when somebody looks at solution.U
+        if self.member_errors:
+            m, e = next(iter(self.member_errors.items()))
+            raise AssertionError(f"member {m}: {e}")
+        return self.solutions
+
+    def close(self, fetch_U=True):
+        """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""
+        if self._batch is not None:
+            for s in self.solvers:
+                sol = s.solution
+                if fetch_U:
+                    _ = sol.U
+                else:
+                    sol._bind_device_U(sol.__dict__.get('_U'), track=False)
+                s._engine = None
+            self._batch.close()
+            self._batch = None
+
+    def __del__(self):
+        try:
+            self.close(fetch_U=False)
+        except Exception:
+            pass

@@ -1,0 +1,339 @@
+// chs_batch.hip -- the batch of include/chs_hip.h: B ensemble members of one N, element type and device advance
+// through the fast engine's step loop together, every step kernel launched ONCE for all of them.
+//
+// A member is an ordinary engine (chs_create: its own constants, state, field, transform scratch, partial sums and
+// rows ring); the batch gives all of them one stream and keeps a device array of member records (BatchMember,
+// chs_fast_kernels.h) that the batched kernels index by blockIdx.y.  Everything outside the step loop -- field
+// up/downloads, prepare, the entry of a call (hat_U = dctn(U)), the state, the rebuild of U after a stop -- is
+// the single handle's code, run member by member on the shared stream: once per call.  Inside the loop a step is
+//   k_col, k_row_inv<fused>, k_step_tail_batch  [+ k_row_inv<last>, k_step_tail_batch<last> for the members whose
+//   call ends with this step]
+// in stream order: the tail of every member runs right behind its row kernel (no riding, no gate, no second hat_U
+// buffer -- what those hide, the launch latency of one member's short kernels, is covered here by the other
+// members' workgroups).  Every kernel body is the single handle's (the tail with the block size it has there).
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "chs_fast_kernels.h"
+
+// The batch's per-step bookkeeping: one workgroup per member running the single handle's tail body (chs_tail.h) with
+// the single handle's block size -- THREADS = that of the k_col the tail rides in there (LAST = false: the first step's
+// time-step control with `pre_only`, the record + control of the next step otherwise), 1024 for the record of the
+// call's last step (LAST, k_step_tail's) -- so that the sums are added up in the same order.  A member takes part when
+// its running step (st->rows_written) is one of those.  (In a translation unit of its own: beside the k_col
+// instantiations that share step_tail_body<THREADS> it would change how the compiler inlines it there.)
+template <int THREADS, bool LAST>
+__global__ __launch_bounds__(THREADS) void k_step_tail_batch(const BatchMember* __restrict__ mem, int pre_only) {
+  __shared__ double red[TAIL_RED_DOUBLES(THREADS)];
+  const BatchMember& m = mem[blockIdx.x];
+  const long long done = m.st->rows_written, last = m.nsteps - 1;
+  if ((LAST ? done != last : (pre_only ? done > last : done >= last)) || m.st->halt) return;
+  step_tail_body<THREADS>(m.tail[LAST ? 2 : (pre_only ? 0 : 1)], m.st, red);
+}
+
+static int launch_tail(hipStream_t s, const BatchMember* mem, int B, int col_threads, bool last, int pre_only) {
+  if (last) k_step_tail_batch<1024, true><<<B, 1024, 0, s>>>(mem, 0);
+  else if (col_threads == 64) k_step_tail_batch<64, false><<<B, 64, 0, s>>>(mem, pre_only);
+  else if (col_threads == 128) k_step_tail_batch<128, false><<<B, 128, 0, s>>>(mem, pre_only);
+  else if (col_threads == 256) k_step_tail_batch<256, false><<<B, 256, 0, s>>>(mem, pre_only);
+  else { chs_set_error("chs_batch_step_n: no batched tail for this block size"); return CHS_EINVAL; }
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+namespace {
+struct Batch {
+  int B = 0, N = 0, dtype = CHS_F64, device = 0;
+  std::vector<Engine*> m;
+  std::vector<hipStream_t> own;  // the members' own streams, handed back at chs_batch_destroy
+  hipStream_t stream = nullptr;
+  BatchMember* dMem = nullptr;
+  std::vector<BatchMember> hMem;
+  DevState* hPoll = nullptr;     // pinned [5][B]: slot 0 = the end of a call, 1..4 = the polls behind the step batches
+  hipEvent_t evPoll[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
+
+int bad(const std::string& s) { chs_set_error(s); return CHS_EINVAL; }
+
+void batch_free(Batch* b) {
+  if (!b) return;
+  hipSetDevice(b->device);
+  if (b->stream) hipStreamSynchronize(b->stream);
+  for (size_t i = 0; i < b->m.size(); ++i) {
+    if (!b->m[i]) continue;
+    if (i < b->own.size() && b->own[i]) b->m[i]->stream = b->own[i];
+    chs_destroy((chs_handle)b->m[i]);
+  }
+  if (b->dMem) hipFree(b->dMem);
+  if (b->hPoll) hipHostFree(b->hPoll);
+  for (auto e : b->evPoll) if (e) hipEventDestroy(e);
+  if (b->stream) hipStreamDestroy(b->stream);
+  delete b;
+}
+
+Batch* as_batch(chs_batch h) { return (Batch*)h; }
+}  // namespace
+
+extern "C" int chs_batch_create(const chs_consts* consts, int32_t B, const double* lambda, chs_batch* out) {
+  if (!consts || !lambda || !out) return bad("chs_batch_create: null argument");
+  *out = nullptr;
+  if (B < 1) return bad("chs_batch_create: B must be >= 1");
+  const chs_consts& c0 = consts[0];
+  for (int i = 0; i < B; ++i) {
+    const chs_consts& c = consts[i];
+    const std::string who = "chs_batch_create: member " + std::to_string(i) + ": ";
+    if (c.N != c0.N || c.dtype != c0.dtype || c.device != c0.device)
+      return bad(who + "every member needs the N, dtype and device of member 0");
+    if (!batch_n_ok(c.N)) return bad(who + "a batch needs N in {128, 256, 512, 1024, 2048}");
+    if (c.engine == CHS_ENGINE_DIRECT) return bad(who + "a batch runs the fast engine only (engine=direct given)");
+    if (c.engine != CHS_ENGINE_AUTO && c.engine != CHS_ENGINE_FAST) return bad(who + "bad engine");
+    if (c.adaptive_time) return bad(who + "a batch takes a fixed time step only (adaptive_time given)");
+  }
+  Batch* b = new (std::nothrow) Batch();
+  if (!b) return bad("out of host memory");
+  b->B = B; b->N = c0.N; b->dtype = c0.dtype; b->device = c0.device;
+  auto fail = [&](int rc) { batch_free(b); return rc; };
+  for (int i = 0; i < B; ++i) {
+    chs_consts c = consts[i];
+    c.engine = CHS_ENGINE_FAST;
+    chs_handle h = nullptr;
+    const int rc = chs_create(&c, lambda, &h);
+    if (rc) return fail(rc);
+    b->m.push_back((Engine*)h);
+  }
+  FastPlan* P = (FastPlan*)b->m[0]->dTw;
+  if (!P || !P->col_batch) return fail(bad("chs_batch_create: no batched kernels for this configuration"));
+#define TRY_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { chs_hip_fail(e__, #call, __FILE__, __LINE__); return fail(CHS_EHIP); } } while (0)
+  TRY_HIP(hipSetDevice(b->device));
+  int rc;
+  if ((rc = P->init_batch())) return fail(rc);
+  TRY_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  for (Engine* E : b->m) {   // one stream for all members: their own launches and the batched ones stay in order
+    TRY_HIP(hipStreamSynchronize(E->stream));
+    b->own.push_back(E->stream);
+    E->stream = b->stream;
+  }
+  TRY_HIP(hipMalloc(&b->dMem, sizeof(BatchMember) * (size_t)B));
+  TRY_HIP(hipHostMalloc((void**)&b->hPoll, sizeof(DevState) * 5 * (size_t)B, hipHostMallocDefault));
+  for (auto& e : b->evPoll) TRY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+#undef TRY_HIP
+  b->hMem.resize((size_t)B);
+  *out = (chs_batch)b;
+  return CHS_OK;
+}
+
+extern "C" int chs_batch_destroy(chs_batch h) {
+  batch_free(as_batch(h));
+  return CHS_OK;
+}
+
+// member m, or every member for m = -1
+template <class F>
+static int each_member(Batch* b, int32_t member, const char* what, F&& f) {
+  if (!b) { chs_set_error(std::string(what) + ": null handle"); return CHS_EINVAL; }
+  if (member < -1 || member >= b->B) { chs_set_error(std::string(what) + ": no such member"); return CHS_EINVAL; }
+  const int lo = member < 0 ? 0 : member, hi = member < 0 ? b->B : member + 1;
+  for (int i = lo; i < hi; ++i) {
+    const int rc = f(i, (chs_handle)b->m[i]);
+    if (rc) return rc;
+  }
+  return CHS_OK;
+}
+
+extern "C" int chs_batch_set_U(chs_batch h, int32_t member, const double* host_U) {
+  return each_member(as_batch(h), member, "chs_batch_set_U", [&](int, chs_handle e) { return chs_set_U(e, host_U); });
+}
+
+extern "C" int chs_batch_init_U_pcg64(chs_batch h, int32_t member, double base, double scale, const uint64_t state[2],
+                                      const uint64_t inc[2]) {
+  return each_member(as_batch(h), member, "chs_batch_init_U_pcg64",
+                     [&](int, chs_handle e) { return chs_init_U_pcg64(e, base, scale, state, inc); });
+}
+
+extern "C" int chs_batch_get_U(chs_batch h, int32_t member, double* host_U) {
+  if (member < 0) return bad("chs_batch_get_U: one member at a time");
+  return each_member(as_batch(h), member, "chs_batch_get_U", [&](int, chs_handle e) { return chs_get_U(e, host_U); });
+}
+
+extern "C" int chs_batch_get_state(chs_batch h, int32_t member, chs_state* out) {
+  if (member < 0) return bad("chs_batch_get_state: one member at a time");
+  return each_member(as_batch(h), member, "chs_batch_get_state", [&](int, chs_handle e) { return chs_get_state(e, out); });
+}
+
+extern "C" int chs_batch_set_state(chs_batch h, int32_t member, const chs_state* in) {
+  if (member < 0) return bad("chs_batch_set_state: one member at a time");
+  return each_member(as_batch(h), member, "chs_batch_set_state", [&](int, chs_handle e) { return chs_set_state(e, in); });
+}
+
+// chs_prepare of every member; a member whose step-0 record is NaN does not keep the others from being prepared
+extern "C" int chs_batch_prepare(chs_batch h, double* rows0) {
+  if (!rows0) return bad("chs_batch_prepare: null argument");
+  int nan = 0;
+  const int rc = each_member(as_batch(h), -1, "chs_batch_prepare", [&](int i, chs_handle e) {
+    const int r = chs_prepare(e, rows0 + 9 * (size_t)i);
+    if (r == CHS_ENAN) { nan = 1; return CHS_OK; }
+    return r;
+  });
+  if (rc) return rc;
+  if (nan) { chs_set_error("chs_batch_prepare: NaN in a step-0 record (timedata.py:10)"); return CHS_ENAN; }
+  return CHS_OK;
+}
+
+// rows of member i, [from, to) of its ring -> the caller's array
+static int copy_member_rows(Engine* E, double* rows, int64_t from, int64_t to) {
+  while (from < to) {
+    const int64_t slot = from % E->rowsCap;
+    int64_t n = to - from;
+    if (slot + n > E->rowsCap) n = E->rowsCap - slot;
+    CHS_HIP(hipMemcpy(rows + from * 9, E->dRows + slot * 9, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
+    from += n;
+  }
+  return CHS_OK;
+}
+
+// chs_step_n of every member as a literal solve_or_resume call (hat_U = dctn(U) on entry, U stored at the end), the
+// steps of all members issued together.  As in chs_step_n the steps go out in batches, and behind every batch the
+// members' states are fetched; once every member that still has steps to do has halted nothing more is issued.
+extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flags, double* rows, int64_t* steps_done,
+                                int32_t* status) {
+  Batch* b = as_batch(h);
+  if (!b || !nsteps || !steps_done || !status) return bad("chs_batch_step_n: null argument");
+  if (flags != 0) return bad("chs_batch_step_n: flags is reserved and must be 0");
+  const int B = b->B;
+  int64_t maxn = 0;
+  for (int i = 0; i < B; ++i) {
+    if (nsteps[i] > 0 && !b->m[i]->prepared) {
+      chs_set_error("chs_batch_step_n: member " + std::to_string(i) + " not prepared (solver.py:139)");
+      return CHS_ESTATE;
+    }
+    if (nsteps[i] > maxn) maxn = nsteps[i];
+  }
+  if (maxn > 0 && !rows) return bad("chs_batch_step_n: rows is null");
+  CHS_HIP(hipSetDevice(b->device));
+  int rc;
+  int batch_steps = 1024;
+  // entry of every member that runs: re-armed loop, hat_U = dctn(U) and the first step's row transform of EnergieEut(U)
+  for (int i = 0; i < B; ++i) {
+    Engine* E = b->m[i];
+    BatchMember& r = b->hMem[(size_t)i];
+    std::memset((void*)&r, 0, sizeof r);
+    const int64_t n = nsteps[i] > 0 ? nsteps[i] : 0;
+    r.nsteps = n;
+    steps_done[i] = 0;
+    status[i] = CHS_OK;
+    r.st = E->dState;   // (read by every batched kernel: rows_written >= nsteps = 0 keeps the member out)
+    if (n == 0) continue;   // sits the call out: state and field stay as they are
+    E->stateCached = false; E->resident = false; E->keepResident = false;
+    E->tailDeferred = false; E->tailGated = false; E->preRider = false;
+    E->storeU = false;
+    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) batch_steps = E->batchSteps < batch_steps ? E->batchSteps : batch_steps;
+    if ((rc = chs_launch_call_begin(E))) return rc;
+    if ((rc = chs_fast_enter_fused(E))) return rc;   // (selects the partial-sum set the whole call uses)
+    E->hat_valid = true;
+    r.dc = E->dc;
+    r.T1 = E->dT1;
+    r.T2 = CHS_ALIAS_T ? E->dT1 : E->dT2;
+    r.hat = E->dHat;
+    r.U = E->dU;
+    r.partDiag = E->dPartDiag; r.partMu = E->dPartMu; r.partRa = E->dPartRa; r.partE2 = E->dPartE2;
+    r.tail[0] = chs_tail_args(E, -1, 1);
+    r.tail[0].pre_only = 1;
+    r.tail[1] = chs_tail_args(E, -1, 1);
+    r.tail[2] = chs_tail_args(E, -1, 0);
+  }
+  if (const char* bs = getenv("CHS_BATCH_STEPS")) {   // (the test hook of chs_step_n: small batches exercise the polls)
+    const long v = atol(bs);
+    if (v >= 1 && v <= 8192) batch_steps = (int)v;
+  }
+  CHS_HIP(hipMemcpyAsync(b->dMem, b->hMem.data(), sizeof(BatchMember) * (size_t)B, hipMemcpyHostToDevice, b->stream));
+  Engine* E0 = b->m[0];
+  FastPlan* P = (FastPlan*)E0->dTw;
+  std::vector<int64_t> copied((size_t)B, 0);
+  if (maxn > 0) {
+    if ((rc = launch_tail(b->stream, b->dMem, B, P->col_threads, false, 1))) return rc;
+  }
+  int64_t issued = 0;
+  int poll = 0;
+  bool stopped = false;
+  while (issued < maxn && !stopped) {
+    int64_t nb = maxn - issued;
+    if (nb > batch_steps) nb = batch_steps;
+    for (int64_t s = issued; s < issued + nb; ++s) {
+      bool go_on = false, last = false;
+      for (int i = 0; i < B; ++i) {
+        go_on |= s < nsteps[i] - 1;
+        last |= s == nsteps[i] - 1;
+      }
+      if ((rc = P->col_batch(E0, b->stream, b->dMem, B, (CHS_COL_ZIGZAG && (s & 1)) ? 1 : 0))) return rc;
+      if (go_on && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, true))) return rc;
+      if (last && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, false))) return rc;
+      // (the last-step records first: a member whose record the other launch writes moves on to its last step)
+      if (last && (rc = launch_tail(b->stream, b->dMem, B, P->col_threads, true, 0))) return rc;
+      if (go_on && (rc = launch_tail(b->stream, b->dMem, B, P->col_threads, false, 0))) return rc;
+    }
+    issued += nb;
+    if (issued < maxn) {
+      const int slot = 1 + (poll & 3);
+      for (int i = 0; i < B; ++i)
+        if (nsteps[i] > 0)
+          CHS_HIP(hipMemcpyAsync(&b->hPoll[(size_t)slot * B + i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
+      CHS_HIP(hipEventRecord(b->evPoll[poll & 3], b->stream));
+      if (poll >= 1) {
+        const int prev = (poll - 1) & 3;
+        CHS_HIP(hipEventSynchronize(b->evPoll[prev]));
+        const DevState* ps = &b->hPoll[(size_t)(1 + prev) * B];
+        bool all = true;
+        for (int i = 0; i < B; ++i) {
+          if (nsteps[i] <= 0) continue;
+          const int64_t w = ps[i].rows_written < nsteps[i] ? ps[i].rows_written : nsteps[i];
+          if (w > copied[(size_t)i]) {
+            if ((rc = copy_member_rows(b->m[i], rows + (size_t)i * maxn * 9, copied[(size_t)i], w))) return rc;
+            copied[(size_t)i] = w;
+          }
+          // (the poll is two batches behind: a member that was running then and has steps left now is still going)
+          if (!ps[i].halt && nsteps[i] > issued) all = false;
+        }
+        if (all) stopped = true;
+      }
+      ++poll;
+    }
+  }
+  for (int i = 0; i < B; ++i)
+    if (nsteps[i] > 0)
+      CHS_HIP(hipMemcpyAsync(&b->hPoll[i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
+  CHS_HIP(hipStreamSynchronize(b->stream));
+  bool any_nan = false;
+  for (int i = 0; i < B; ++i) {
+    if (nsteps[i] <= 0) continue;
+    Engine* E = b->m[i];
+    const DevState s = b->hPoll[i];
+    if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && s.rows_written < nsteps[i]) {
+      // the energy rule or the time limit ended this member's call before its last step: its row kernel has been
+      // keeping U in registers and hat_U is that of the last completed step -- the field is rebuilt from it (run_steps)
+      DevState r = s;
+      r.halt = 0;
+      CHS_HIP(hipMemcpy(E->dState, &r, sizeof r, hipMemcpyHostToDevice));
+      if ((rc = chs_fast_recover_u(E))) return rc;
+      CHS_HIP(hipStreamSynchronize(b->stream));
+      CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
+    }
+    if (s.halt) E->hat_valid = false;
+    E->csHost = s.computed_steps;
+    int64_t done = s.rows_written < nsteps[i] ? s.rows_written : nsteps[i];
+    steps_done[i] = done;
+    double* mr = rows + (size_t)i * maxn * 9;
+    if (done > copied[(size_t)i] && (rc = copy_member_rows(E, mr, copied[(size_t)i], done))) return rc;
+    // solver.py:230 `domtime = self.time_passed ** (1 / 3)` with the host libm
+    for (int64_t k = 0; k < done; ++k) mr[k * 9 + 4] = pow(mr[k * 9 + 4], 1.0 / 3.0);
+    if (s.nan_flag) { status[i] = CHS_ENAN; any_nan = true; }
+  }
+  if (any_nan) {
+    chs_set_error("NaN in a recorded scalar (timedata.py:10) of a member: U left (0,1)");
+    return CHS_ENAN;
+  }
+  return CHS_OK;
+}

@@ -79,11 +79,11 @@ using G2048 = FCfg<float, 2048, 64, 256, 8, 16, 1, 8, 2, 0, 8, 2, (CHS_F32_CT_SM
 
 bool chs_fast_bind_f32(int N, FastPlan* P) {
   switch (N) {
-    case 128: bind<G128>(P); break;
-    case 256: bind<G256>(P); break;
-    case 512: bind<G512, G512C>(P); break;
-    case 1024: bind<G1024>(P); break;
-    case 2048: bind<G2048>(P); break;
+    case 128: bind<G128>(P); bind_batch<G128>(P); break;
+    case 256: bind<G256>(P); bind_batch<G256>(P); break;
+    case 512: bind<G512, G512C>(P); bind_batch<G512, G512C>(P); break;
+    case 1024: bind<G1024>(P); bind_batch<G1024>(P); break;
+    case 2048: bind<G2048>(P); bind_batch<G2048>(P); break;
     case 4096: bind<G4096, G4096C>(P); break;
     case 8192: bind<G8192, G8192C>(P); break;
     default: return false;

@@ -124,11 +124,11 @@ template <> struct RowTwLds<F8192> { static constexpr int value = CHS_F8192_ROW_
 
 bool chs_fast_bind_f64(int N, FastPlan* P) {
   switch (N) {
-    case 128: bind<F128>(P); break;
-    case 256: bind<F256>(P); break;
-    case 512: bind<F512, F512C>(P); break;
-    case 1024: bind<F1024>(P); break;
-    case 2048: bind<F2048, F2048C>(P); break;
+    case 128: bind<F128>(P); bind_batch<F128>(P); break;
+    case 256: bind<F256>(P); bind_batch<F256>(P); break;
+    case 512: bind<F512, F512C>(P); bind_batch<F512, F512C>(P); break;
+    case 1024: bind<F1024>(P); bind_batch<F1024>(P); break;
+    case 2048: bind<F2048, F2048C>(P); bind_batch<F2048, F2048C>(P); break;
     case 4096: bind<F4096, F4096C>(P); break;
     case 8192: bind<F8192, F8192C>(P); break;
     default: return false;

@@ -593,6 +593,35 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
 }
 
 // ---------------------------------------------------------------------------
+// Batches (chs_batch.hip): B members of one N and element type advance together, each step kernel launched ONCE
+// for all of them.  The batched instantiations of k_row_inv and k_col take one argument more, the device array of
+// the member records; blockIdx.y is the member.  A workgroup reads its member's record (uniform: scalar loads),
+// takes the member's arrays, state and constants in place of the arguments, and leaves at once when the member
+// has no step left in this call (or has halted: the kernels' own check).  The instantiations without it -- the
+// single handle's -- are the same code as before (an empty pack; `if constexpr` drops the batch part).
+// ---------------------------------------------------------------------------
+struct BatchMember {
+  DevConsts dc;
+  DevState* st;
+  void* T1;   // the step's T operand: k_col in, fused row kernel out
+  void* T2;   // k_col out, k_row_inv in (aliases T1: CHS_ALIAS_T)
+  void* hat;  // hat_U, updated in place (after a stop: that of the last completed step)
+  void* U;
+  double* partDiag; double* partMu; double* partRa; double* partE2;
+  long long nsteps;  // iterations of the running call: the member's step of a launch is st->rows_written
+  TailArgs tail[3];  // the step tail's inputs: [0] first step (time-step control only), [1] record + control of the
+                     // next step, [2] record of the call's last step
+};
+// (read through the constant address space: the records do not change during a launch, so the compiler may load a
+// field again where it is used instead of keeping it in registers across the kernel)
+typedef const __attribute__((address_space(4))) BatchMember ConstBatchMember;
+template <class P>
+__device__ __forceinline__ ConstBatchMember& batch_member(P mem) {
+  static_assert(std::is_same<P, const BatchMember*>::value, "batched launches pass the member records");
+  return ((ConstBatchMember*)mem)[blockIdx.y];
+}
+
+// ---------------------------------------------------------------------------
 // k_row_inv: one group per row: T2 (tile-major) -> DCT-III -> U (row-major, solver.py:208).
 //   DIAG: while U is in registers, the pointwise part of the record of this step
 //         (solver.py:218-228): bulk energy density, |U - mean| and the U < threshold
@@ -602,15 +631,24 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
 //         166-175, sharing log U and log(1-U) with the energy density), sum(mu^2), and
 //         the forward row DCT-II into T1 -- U is never re-read from HBM.
 // ---------------------------------------------------------------------------
-template <class C, bool DIAG, bool FUSE, bool ADAPT = false>
+template <class C, bool DIAG, bool FUSE, bool ADAPT = false, class... Batch>
 __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C::T* __restrict__ T2, typename C::T* __restrict__ U,
                                                     typename C::T* __restrict__ T1, FTables<typename C::T> tb,
                                                     DevConsts dc, const DevState* __restrict__ st,
                                                     double* __restrict__ partDiag, double* __restrict__ partMu,
                                                     double* __restrict__ partRa, int store_u,
-                                                    typename C::T* __restrict__ partColRows = nullptr) {
+                                                    typename C::T* __restrict__ partColRows = nullptr, Batch... mem) {
   using T = typename C::T;
   __shared__ double red[64];
+  if constexpr (sizeof...(Batch) != 0) {
+    // batched (FUSE: the members whose call goes on behind this step; !FUSE: those for which it is the last)
+    static_assert(DIAG && !ADAPT, "batches run the fixed-step row kernels");
+    ConstBatchMember& m = batch_member(mem...);
+    const long long done = m.st->rows_written, last = m.nsteps - 1;
+    if (FUSE ? done >= last : done != last) return;
+    T2 = (const T*)m.T2; U = (T*)m.U; T1 = (T*)m.T1; dc = *(const DevConsts*)&m.dc; st = m.st;
+    partDiag = m.partDiag; partMu = m.partMu; partRa = m.partRa;
+  }
   if (st->halt) return;
   T* lds = reinterpret_cast<T*>(chs_dyn_lds);
   const int wv = chs_wave_id();   // (threadIdx.x is not kept across the kernel: chs_common.h)
@@ -983,14 +1021,21 @@ constexpr int col_lds_elems() {
   return (ColDma<C>::value && 2 * DmaStage<C>::ZONE > base) ? 2 * DmaStage<C>::ZONE : base;
 }
 
-template <class C, int MODE>
+template <class C, int MODE, class... Batch>
 __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T* __restrict__ Tin, typename C::T* __restrict__ Tout,
                                                 typename C::T* __restrict__ hat, typename C::T* __restrict__ nat,
                                                 FTables<typename C::T> tb, const double* __restrict__ lam,
                                                 const double* __restrict__ sinsq, DevState* __restrict__ st,
-                                                double* __restrict__ partE2, TailArgs ta) {
+                                                double* __restrict__ partE2, TailArgs ta, Batch... mem) {
   using T = typename C::T;
   using CS = ColStage<C>;
+  if constexpr (sizeof...(Batch) != 0) {
+    // batched (the members with a step left in this call; nothing rides: the batch's tail is a launch of its own)
+    static_assert(MODE == MODE_STEP, "batches launch the step's column pass only");
+    ConstBatchMember& m = batch_member(mem...);
+    if (m.st->rows_written >= m.nsteps) return;
+    Tin = (const T*)m.T1; Tout = CHS_ALIAS_T ? (T*)m.T1 : (T*)m.T2; hat = (T*)m.hat; st = m.st; partE2 = m.partE2;
+  }
   __shared__ double red[32];
   // MODE_STEP: block 0 of this very launch may raise the stop flag (the riding tail, a gate that timed out): one thread
   // reads it for the whole workgroup, so that all its wavefronts leave or stay together.  EARLY_HALT: at the very top, in
@@ -1529,6 +1574,12 @@ struct FastPlan {
   int (*row_inv)(Engine*, int, const void*, void*, void*) = nullptr;
   int (*col)(Engine*, int, const void*, void*, void*, void*) = nullptr;
   int (*init)(Engine*) = nullptr;
+  // batched step kernels (N <= 2048; nullptr where no batch is offered): E0 = any member (tables, lambda),
+  // `mem` = the device array of the B member records
+  int (*init_batch)() = nullptr;
+  int (*col_batch)(Engine* E0, hipStream_t s, const BatchMember* mem, int B, int reverse) = nullptr;
+  int (*row_inv_batch)(Engine* E0, hipStream_t s, const BatchMember* mem, int B, bool fuse) = nullptr;
+  int col_threads = 0;   // block size of the step's k_col: that of the single handle's riding tail (chs_batch.hip)
 };
 
 template <typename T>
@@ -1663,6 +1714,47 @@ struct Launch {
     return CHS_OK;
   }
 };
+
+template <class C, class CC = C>
+struct BatchLaunch {
+  using T = typename C::T;
+  using L = Launch<C, CC>;
+  static int init() {
+    int rc;
+    if ((rc = L::set_lds(k_col<CC, MODE_STEP, const BatchMember*>, L::col_lds))) return rc;
+    if ((rc = L::set_lds(k_row_inv<C, true, true, false, const BatchMember*>, L::row_lds))) return rc;
+    return L::set_lds(k_row_inv<C, true, false, false, const BatchMember*>, L::row_lds);
+  }
+  static int col(Engine* E0, hipStream_t s, const BatchMember* mem, int B, int reverse) {
+    TailArgs ta;
+    ta.reverse = reverse;
+    k_col<CC, MODE_STEP, const BatchMember*><<<dim3(CC::N / CC::C, B), CC::THREADS, L::col_lds, s>>>(
+        nullptr, nullptr, nullptr, nullptr, get_tables<T>(E0), E0->dLambda, E0->dSinSq, nullptr, nullptr, ta, mem);
+    CHS_HIP(hipGetLastError());
+    return CHS_OK;
+  }
+  static int row_inv(Engine* E0, hipStream_t s, const BatchMember* mem, int B, bool fuse) {
+    const dim3 grid(C::N / C::C, B);
+    const FTables<T> tb = get_tables<T>(E0);
+    if (fuse)
+      k_row_inv<C, true, true, false, const BatchMember*><<<grid, C::THREADS, L::row_lds, s>>>(
+          nullptr, nullptr, nullptr, tb, E0->dc, nullptr, nullptr, nullptr, nullptr, 0, nullptr, mem);
+    else
+      k_row_inv<C, true, false, false, const BatchMember*><<<grid, C::THREADS, L::row_lds, s>>>(
+          nullptr, nullptr, nullptr, tb, E0->dc, nullptr, nullptr, nullptr, nullptr, 1, nullptr, mem);
+    CHS_HIP(hipGetLastError());
+    return CHS_OK;
+  }
+};
+
+// the batched step kernels of a configuration (chs_fast_f64.hip / chs_fast_f32.hip: N <= 2048)
+template <class C, class CC = C>
+static void bind_batch(FastPlan* P) {
+  P->init_batch = &BatchLaunch<C, CC>::init;
+  P->col_batch = &BatchLaunch<C, CC>::col;
+  P->row_inv_batch = &BatchLaunch<C, CC>::row_inv;
+  P->col_threads = CC::THREADS;
+}
 
 template <class C, class CC = C>
 static void bind(FastPlan* P) {

@@ -107,6 +107,22 @@ def run_params(init_params: Parameters, run_id, rand_values, A_list):
     return params, fac_A0, fac_A1
 
 
+def _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess):
+    """The 12-tuple of experiment.py:114-126 from a finished run."""
+    ca = cb = sa = sb = float('nan')
+    if postprocess:
+        # experiment.py:110-112 -- a failure here (sympy missing, no common tangent, not exactly two
+        # spinodal roots) is an error of the run, as in the reference: a silent NaN would poison
+        # -results-agg.csv.  postprocess=False skips the thermodynamic columns explicitly.
+        with _SYMPY_LOCK:
+            cgap = utils.get_miscibility_gap(params.R, params.temp, params.B, solution.A0, solution.A1)
+            ca, cb = float(cgap[0]), float(cgap[1])
+            sa, sb = (float(r) for r in utils.get_roots_of_EPP(params.R, params.temp, solution.A0, solution.A1))
+    itargmax = int(np.argmax(solution.E2))
+    return (solution.A0, solution.A1, ca, cb, sa, sb, solution.tau0, solution.t0, itargmax, run_id,
+            np.nan if fac_A0 is None else fac_A0, np.nan if fac_A1 is None else fac_A1)
+
+
 def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True):
     """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126."""
     from .simulator import Simulator
@@ -115,21 +131,34 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
     try:
         solution = simulator.solve()
         simulator.export()
-        ca = cb = sa = sb = float('nan')
-        if postprocess:
-            # experiment.py:110-112 -- a failure here (sympy missing, no common tangent, not exactly two
-            # spinodal roots) is an error of the run, as in the reference: a silent NaN would poison
-            # -results-agg.csv.  postprocess=False skips the thermodynamic columns explicitly.
-            with _SYMPY_LOCK:
-                cgap = utils.get_miscibility_gap(params.R, params.temp, params.B, solution.A0, solution.A1)
-                ca, cb = float(cgap[0]), float(cgap[1])
-                sa, sb = (float(r) for r in utils.get_roots_of_EPP(params.R, params.temp, solution.A0, solution.A1))
-        itargmax = int(np.argmax(solution.E2))
+        rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
         # the record needs scalars only; an exception above must not leak the engine either (it goes back to the pool)
         simulator.solver.close(fetch_U=False)
-    return (solution.A0, solution.A1, ca, cb, sa, sb, solution.tau0, solution.t0, itargmax, run_id,
-            np.nan if fac_A0 is None else fac_A0, np.nan if fac_A1 is None else fac_A1)
+    return rec
+
+
+def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True):
+    """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
+    run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple."""
+    from .batch import BatchSolver
+    from .simulator import Simulator
+    runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
+    bs = BatchSolver([r[0] for r in runs], U_init)
+    try:
+        bs.prepare()
+        solutions = bs.solve_or_resume()
+        recs = []
+        for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
+            # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
+            sim = Simulator.__new__(Simulator)
+            sim.params, sim.solver = params, bs.solvers[m]
+            sim.solution_file_id = utils.get_or_create_file_id(params.file_id)
+            sim.export()
+            recs.append(_member_record(i, params, solutions[m], fac_A0, fac_A1, postprocess))
+    finally:
+        bs.close(fetch_U=False)
+    return recs
 
 
 def my_run_ids(nr_items, rank, world):
@@ -181,19 +210,37 @@ def write_results(file_id, records):
 
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
-                 concurrent=1):
+                 concurrent=1, batch=0, batch_fn=None):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
     ``concurrent`` members of a rank run at the same time (one engine handle = one HIP stream each;
     the C ABI calls release the GIL): at ensemble sizes such as N=2048 a single run leaves the GPU
-    partly idle between its latency-bound kernels, two or three concurrent runs fill the gaps."""
+    partly idle between its latency-bound kernels, two or three concurrent runs fill the gaps.
+
+    ``batch`` > 0: the rank's members run ``batch`` at a time as one device workload, every step kernel launched
+    once for the whole group (``batch_fn(run_ids, init_params, rand_values, A_list)`` -> their 12-tuples; default
+    run_batch_gpu).  A configuration outside the batch's scope (chsimpy_amd.batch.scope_error) runs member by
+    member instead, with a note."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
             return run_experiment_gpu(run_id, p, rv, al, U_init)
     ids = my_run_ids(nr_items, rank, world)
-    if concurrent > 1 and len(ids) > 1:
+    if batch > 0 and batch_fn is None:
+        from .batch import scope_error
+        why = scope_error(init_params)
+        if why:
+            print(f"chsimpy_amd.experiment: --batch {batch} not taken ({why}); members run one by one")
+            batch = 0
+        else:
+            def batch_fn(run_ids, p, rv, al):
+                return run_batch_gpu(run_ids, p, rv, al, U_init)
+    if batch > 0:
+        local = []
+        for k in range(0, len(ids), batch):
+            local.extend(batch_fn(ids[k:k + batch], init_params, rand_values, A_list))
+    elif concurrent > 1 and len(ids) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=concurrent) as pool:
             local = list(pool.map(lambda i: run_fn(i, init_params, rand_values, A_list), ids))
@@ -209,6 +256,11 @@ def _dry_member(run_id, init_params, rand_values, A_list):
     a0, a1 = params.func_A0(params.temp), params.func_A1(params.temp)
     return (a0, a1, 0.1, 0.9, 0.2, 0.8, 100 + run_id, 1.5 * run_id, 7 * run_id, run_id,
             np.nan if f0 is None else f0, np.nan if f1 is None else f1)
+
+
+def _dry_batch(run_ids, init_params, rand_values, A_list):
+    """`--dry-run --batch B`: a group of members without device work (see _dry_member)."""
+    return [_dry_member(i, init_params, rand_values, A_list) for i in run_ids]
 
 
 def _launch_own_ranks(a, argv):
@@ -249,6 +301,8 @@ def main(argv=None):
     ap.add_argument('--export-csv', default=None)
     ap.add_argument('--Uinit-file', default=None)
     ap.add_argument('--concurrent', type=int, default=2, help='ensemble members running at once per GPU')
+    ap.add_argument('--batch', type=int, default=0, help='advance a rank\'s members this many at a time as one device '
+                    'workload (0: one member per engine handle, see --concurrent)')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
     ap.add_argument('--backend', default=os.environ.get('CHS_DIST_BACKEND', 'nccl'),
@@ -293,9 +347,11 @@ def main(argv=None):
     if rank == 0:
         write_metadata(p.file_id, ep, extra=[f"ranks, {world}", f"concurrent_per_rank, {a.concurrent}",
                                              f"host_cores_per_rank, {'all' if pinned is None else len(pinned)}"]
+                       + ([f"batch_per_rank, {a.batch}"] if a.batch > 0 else [])
                        + (["dry_run, True"] if a.dry_run else []))
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
-                           world=world, device=device, concurrent=a.concurrent)
+                           world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
+                           batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)

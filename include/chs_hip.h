@@ -224,6 +224,36 @@ double chs_last_step_ms(chs_handle h);
 const char* chs_last_error(void);
 const char* chs_version(void);
 
+/* ---- Batches: B ensemble members advanced together --------------------------------------------------------------
+ * A batch holds B members of the same N, dtype and device (the fast engine, N in {128, 256, 512, 1024, 2048}, a fixed
+ * time step); every other scalar of chs_consts -- A0, A1, full_sim, time_limit_s, delt, threshold, ... -- is the
+ * member's own.  Each step kernel is launched once for all members, so that the short dependent chains of small grids
+ * overlap each other on the device.  For every member m the semantics are those of chs_prepare / chs_step_n /
+ * chs_get_state on a single handle created from consts[m]; every chs_batch_step_n is a literal solve_or_resume call
+ * (hat_U = dctn(U) recomputed on entry, solver.py:159; U stored at the end).  One lambda table for all members.
+ * chs_batch_create returns CHS_EINVAL (chs_last_error says why) for B < 1, members that differ in N, dtype or device,
+ * an N outside the set above, engine = CHS_ENGINE_DIRECT, or adaptive_time != 0 in any member.  Jitter has no
+ * batched counterpart.  `member` = -1 addresses every member where noted. */
+typedef struct chs_batch_s* chs_batch;
+int chs_batch_create(const chs_consts* consts /*[B]*/, int32_t B, const double* lambda, chs_batch* out);
+int chs_batch_destroy(chs_batch b);
+int chs_batch_set_U(chs_batch b, int32_t member, const double* host_U);           /* member -1: all */
+int chs_batch_init_U_pcg64(chs_batch b, int32_t member, double base, double scale,
+                           const uint64_t state[2], const uint64_t inc[2]);        /* member -1: all */
+int chs_batch_get_U(chs_batch b, int32_t member, double* host_U);
+/* chs_prepare of every member; rows0[m] = member m's step-0 record.  CHS_ENAN when one of them is NaN (the others
+ * are prepared all the same). */
+int chs_batch_prepare(chs_batch b, double* rows0 /*[B][9]*/);
+/* nsteps[m] iterations of member m (0: the member sits the call out, its state and field unchanged); `flags` is
+ * reserved and must be 0.  rows[m] (stride: the largest nsteps) receives member m's timedata rows, steps_done[m] how
+ * many, status[m] CHS_OK or CHS_ENAN.  A member that stops (energy rule, time limit, NaN) is frozen while the others
+ * go on; the call ends when every member has halted or done its steps.  Returns CHS_ENAN when any member hit NaN (the
+ * rows of the others stay valid).  chs_batch_get_U(m) afterwards returns the field of m's last completed step. */
+int chs_batch_step_n(chs_batch b, const int64_t* nsteps /*[B]*/, int32_t flags,
+                     double* rows /*[B][max nsteps][9]*/, int64_t* steps_done /*[B]*/, int32_t* status /*[B]*/);
+int chs_batch_get_state(chs_batch b, int32_t member, chs_state* out);
+int chs_batch_set_state(chs_batch b, int32_t member, const chs_state* in);
+
 #ifdef __cplusplus
 }
 #endif

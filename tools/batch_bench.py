@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Aggregate member-steps/s of the batch (chsimpy_amd.BatchSolver) against one single handle and against
+run_ensemble(concurrent=3) at the same N.
+
+Protocol: full_sim, one literal 2000-step call (solve_or_resume(2001) after prepare), 1 warm-up + 3 timed repetitions
+(mean and best); members with the A factors of make_rand_values.  Extra rows: 64 x N=2048 (configs[4]'s size) and the
+default experiment (N=512, energy stop, ntmax 1e6, 64 members stopping at different steps).
+
+usage: tools/batch_bench.py [--quick]     (--quick: N=512 fp64 only, B in {1, 16})
+"""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import chsimpy_amd  # noqa: E402
+from chsimpy_amd import experiment as ex  # noqa: E402
+from chsimpy_amd.batch import BatchSolver  # noqa: E402
+
+KAPPA = 0.0002989112919661156
+STEPS = 2000
+REPS = 3
+
+
+def members(N, B, dtype='float64', ntmax=STEPS + 1, full_sim=True):
+    init = chsimpy_amd.Parameters()
+    init.N, init.ntmax, init.full_sim, init.kappa_tilde, init.dtype = N, ntmax, full_sim, KAPPA, dtype
+    init.file_id = '/tmp/batch_bench'
+    ep = ex.ExperimentParams()
+    ep.runs = B
+    rv, al, _ = ex.make_rand_values(ep)
+    return init, ep, [ex.run_params(init, i, rv, al)[0] for i in range(B)]
+
+
+def timed(fn, reps=REPS):
+    fn()                                  # warm-up
+    ts = []
+    for _ in range(reps):
+        ts.append(fn())
+    return float(np.mean(ts)), float(np.min(ts))
+
+
+def single(N, dtype):
+    _, _, ps = members(N, 1, dtype)
+    s = chsimpy_amd.Solver(ps[0])
+    s.rederive_hat = True
+
+    def run():
+        s.prepare()
+        t0 = time.perf_counter()
+        s.solve_or_resume(STEPS + 1)
+        return time.perf_counter() - t0
+    mean, best = timed(run)
+    s.close(fetch_U=False)
+    return STEPS / mean, STEPS / best
+
+
+def batched(N, B, dtype):
+    _, _, ps = members(N, B, dtype)
+    bs = BatchSolver(ps)
+
+    def run():
+        bs.prepare()
+        t0 = time.perf_counter()
+        bs.solve_or_resume(STEPS + 1)
+        return time.perf_counter() - t0
+    mean, best = timed(run)
+    assert all(s.solution.computed_steps == STEPS + 1 for s in bs.solvers)
+    bs.close(fetch_U=False)
+    return B * STEPS / mean, B * STEPS / best
+
+
+def concurrent3(N, dtype, runs=6):
+    init, ep, _ = members(N, runs, dtype)
+
+    def run():
+        t0 = time.perf_counter()
+        ex.run_ensemble(init, ep, concurrent=3,
+                        run_fn=lambda i, p, rv, al: ex.run_experiment_gpu(i, p, rv, al, None, postprocess=False))
+        return time.perf_counter() - t0
+    mean, best = timed(run, reps=2)
+    return runs * STEPS / mean, runs * STEPS / best
+
+
+def default_experiment(B=64, batch=16):
+    """N=512, energy stop, ntmax 1e6: the reference's default experiment, members stopping at different steps."""
+    init, ep, ps = members(512, B, ntmax=int(1e6), full_sim=False)
+    out = {}
+    for label, kw in (('concurrent=1', dict(concurrent=1)), (f'batch={batch}', dict(batch=batch))):
+        t0 = time.perf_counter()
+        recs = ex.run_ensemble(init, ep, run_fn=None if 'batch' in label else
+                               (lambda i, p, rv, al: ex.run_experiment_gpu(i, p, rv, al, None, postprocess=False)),
+                               batch_fn=(lambda ids, p, rv, al: ex.run_batch_gpu(ids, p, rv, al, None, postprocess=False))
+                               if 'batch' in label else None, **kw)
+        dt = time.perf_counter() - t0
+        steps = sum(int(r[6]) for r in recs)
+        out[label] = (dt, steps, sorted(set(int(r[6]) for r in recs)))
+    return out
+
+
+def main():
+    quick = '--quick' in sys.argv
+    rows = ([(512, 'float64')] if quick else
+            [(256, 'float64'), (512, 'float64'), (1024, 'float64'), (2048, 'float64'), (512, 'float32')])
+    Bs = (1, 16) if quick else (1, 4, 16, 64)
+    print(f"# batch bench: full_sim, one literal {STEPS}-step call, 1 warm-up + {REPS} reps; member-steps/s mean (best)")
+    for N, dt in rows:
+        s_mean, s_best = single(N, dt)
+        print(f"N={N} {dt} single handle: {s_mean:9.0f} ({s_best:9.0f}) steps/s", flush=True)
+        c_mean, c_best = concurrent3(N, dt)
+        print(f"N={N} {dt} run_ensemble(concurrent=3, 6 runs, end to end): {c_mean:9.0f} ({c_best:9.0f}) member-steps/s",
+              flush=True)
+        for B in Bs:
+            b_mean, b_best = batched(N, B, dt)
+            print(f"N={N} {dt} batch B={B:3d}: {b_mean:9.0f} ({b_best:9.0f}) member-steps/s   "
+                  f"x{b_mean / s_mean:5.2f} single, x{b_mean / c_mean:5.2f} concurrent=3", flush=True)
+    if not quick:
+        r = default_experiment()
+        for label, (dt, steps, stops) in r.items():
+            print(f"default experiment N=512 energy stop, 64 members, {label}: {dt:7.2f} s, {steps} member-steps "
+                  f"({steps / dt:9.0f}/s), stop steps {stops[0]}..{stops[-1]} ({len(stops)} distinct)", flush=True)
+
+
+if __name__ == '__main__':
+    main()
