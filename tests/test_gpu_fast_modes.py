@@ -115,6 +115,9 @@ def test_adaptive_time_fast_engine(gpu, N, chunks):
     for c in chunks:
         sol = s.solve_or_resume(c); o.solve_or_resume(c)
         assert sol.computed_steps == o.computed_steps
+        # the energy rule keeps watching while the run goes on (full_sim=True): tau0 / t0 recorded once, at the same step
+        assert (sol.tau0, s.skip_check) == (o.tau0, o.skip_check), (c, sol.tau0, o.tau0)
+        assert sol.t0 == pytest.approx(o.t0, rel=1e-9)
     assert s._engine.engine == 'fast'
     td, to = sol.timedata.data(), o.timedata.data()
     assert td.shape == to.shape == (600, 9)
@@ -122,7 +125,7 @@ def test_adaptive_time_fast_engine(gpu, N, chunks):
     assert np.allclose(td[:, 8], to[:, 8], rtol=1e-9, atol=0), relerr(td[:, 8], to[:, 8])
     for c in (1, 2, 4, 5, 6, 7):
         assert np.allclose(td[:, c], to[:, c], rtol=1e-8, atol=1e-300), (c, relerr(td[:, c], to[:, c]))
-    log_line(f"adaptive fast N={N} chunks={chunks}: max rel err delt={relerr(td[:, 8], to[:, 8]):.3e} E={relerr(td[:, 1], to[:, 1]):.3e} "
+    log_line(f"adaptive fast N={N} chunks={chunks}: tau0 {o.tau0} max rel err delt={relerr(td[:, 8], to[:, 8]):.3e} E={relerr(td[:, 1], to[:, 1]):.3e} "
              f"E2={relerr(td[:, 2], to[:, 2]):.3e} U={relerr(sol.U, o.U):.3e}")
     assert np.array_equal(td[:, 3], to[:, 3])                    # SA: a count
     assert np.allclose(sol.U, o.U, rtol=1e-8, atol=0), relerr(sol.U, o.U)
