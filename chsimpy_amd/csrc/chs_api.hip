@@ -66,6 +66,9 @@ static void timer_harvest(Engine* E) {
 // ---------------------------------------------------------------------------
 #define CHS_ROWS_STAGED 4096  // rows of the pinned staging buffer for short calls (run_steps)
 #define CHS_ROWS_RING 65536  // rows of the device ring (4.7 MB), a multiple of the batch size of run_steps
+#define CHS_STEPS_PER_BATCH 1024  // steps issued between two looks at the device's halt flag (run_steps); a quarter of it
+                                  // with a stop rule armed (read_env_hooks, where the environment's CHS_BATCH_STEPS overrides it)
+static_assert(CHS_ROWS_RING % CHS_STEPS_PER_BATCH == 0 && CHS_ROWS_RING >= 8 * CHS_STEPS_PER_BATCH, "ring and batch size");
 
 // timedata rows of the running call: one allocation for the handle's lifetime, used as a ring (run_steps)
 static int ensure_rows(Engine* E) {
@@ -82,16 +85,8 @@ static void free_engine(Engine* E) {
   if (E->engine == CHS_ENGINE_FAST) chs_fast_free(E);
   chs_pointwise_free(E);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
-  if (E->dSlab) {
-    // T and hat_U came as one allocation; the two hat_U pointers may have changed places (stop-rule runs of the small grids)
-    void* slab_hat = (char*)E->dSlab + (size_t)E->N * E->N * E->esz;
-    if (E->dHat && E->dHat != slab_hat) hipFree(E->dHat);
-    if (E->dHat2 && E->dHat2 != slab_hat) hipFree(E->dHat2);
-    hipFree(E->dSlab);
-  } else {
-    hipFree(E->dT1); hipFree(E->dHat);
-    if (E->dHat2) hipFree(E->dHat2);
-  }
+  hipFree(E->dT1); hipFree(E->dHat);
+  if (E->dHat2) hipFree(E->dHat2);
   hipFree(E->dNoise); hipFree(E->dLambda); hipFree(E->dState); hipFree(E->dRows);
   for (auto e : E->timer.pool) hipEventDestroy(e);
   if (E->evA) hipEventDestroy(E->evA);
@@ -133,7 +128,7 @@ static DevState initial_state(const Engine* E) {
 static void read_env_hooks(Engine* E) {
   // with a stop rule armed a call usually ends early: shorter batches, fewer launches issued behind the stop
   // (a launch that finds the stop flag set costs ~2 us; the reference's default run stops at step 1674 of 1e6)
-  E->batchSteps = (!E->dc.full_sim || E->dc.time_limit_s > 0.0) ? 256 : 1024;
+  E->batchSteps = (!E->dc.full_sim || E->dc.time_limit_s > 0.0) ? CHS_STEPS_PER_BATCH / 4 : CHS_STEPS_PER_BATCH;
   if (const char* bs = getenv("CHS_BATCH_STEPS")) {  // test hook: small batches exercise the polling path
     const long v = atol(bs);
     if (v >= 1 && v <= CHS_ROWS_RING / 8) E->batchSteps = (int)v;
@@ -254,21 +249,10 @@ extern "C" int chs_create(const chs_consts* c, const double* lambda, chs_handle*
   const size_t nb = (size_t)N * N * E->esz;
   TRY_HIP(hipMalloc(&E->dU, nb));
   TRY_HIP(hipMalloc(&E->dMU, nb));
-  // CHS_SLAB=1 (experiment): T (the step loop's in-place operand) and hat_U in ONE allocation, back to back -- the two arrays
-  // a step touches as one contiguous range, at N=4096 fp64 exactly the 256 MiB of the Infinity Cache, instead of two ranges an
-  // arbitrary distance apart.  Measured equal (three engines each, both creation orders: 0.9997 / 1.0033; N=8192 fp32 0.9994):
-  // whatever makes two engines of one library differ by up to 1.2 % is not the distance between the two arrays.
-  {
-    const char* e = getenv("CHS_SLAB");
-    if (e && e[0] == '1') {
-      TRY_HIP(hipMalloc(&E->dSlab, 2 * nb));
-      E->dT1 = E->dSlab;
-      E->dHat = (char*)E->dSlab + nb;
-    } else {
-      TRY_HIP(hipMalloc(&E->dT1, nb));
-      TRY_HIP(hipMalloc(&E->dHat, nb));
-    }
-  }
+  // (T and hat_U, the two arrays a step touches, as ONE allocation back to back measured equal -- 0.9997 / 1.0033, N=8192
+  // fp32 0.9994: whatever makes two engines of one library differ by up to 1.2 % is not the distance between the two)
+  TRY_HIP(hipMalloc(&E->dT1, nb));
+  TRY_HIP(hipMalloc(&E->dHat, nb));
   TRY_HIP(hipMalloc(&E->dT2, nb));
   TRY_HIP(hipMalloc(&E->dLambda, sizeof(double) * N));
   TRY_HIP(hipMemcpy(E->dLambda, lambda, sizeof(double) * N, hipMemcpyHostToDevice));
@@ -504,10 +488,6 @@ static int one_step(Engine* E, bool first, bool last) {
 // issued.  The reference's defaults are ntmax = 1e6 with full_sim = False (parameters.py:42,50): a run
 // that stops after a thousand steps must not queue three million empty launches behind the stop.
 // The rows of finished batches are copied out of the device ring as they complete.
-#ifndef CHS_BATCH_STEPS
-#define CHS_BATCH_STEPS 1024
-#endif
-static_assert(CHS_ROWS_RING % CHS_BATCH_STEPS == 0 && CHS_ROWS_RING >= 8 * CHS_BATCH_STEPS, "ring and batch size");
 
 static int copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to) {
   // ring -> caller's array, rows [from, to); at most two pieces

@@ -236,7 +236,7 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     E->hat_valid = true;
     r.dc = E->dc;
     r.T1 = E->dT1;
-    r.T2 = CHS_ALIAS_T ? E->dT1 : E->dT2;
+    r.T2 = E->dT1;
     r.hat = E->dHat;
     r.U = E->dU;
     r.partDiag = E->dPartDiag; r.partMu = E->dPartMu; r.partRa = E->dPartRa; r.partE2 = E->dPartE2;
@@ -268,7 +268,7 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
         go_on |= s < nsteps[i] - 1;
         last |= s == nsteps[i] - 1;
       }
-      if ((rc = P->col_batch(E0, b->stream, b->dMem, B, (CHS_COL_ZIGZAG && (s & 1)) ? 1 : 0))) return rc;
+      if ((rc = P->col_batch(E0, b->stream, b->dMem, B, (s & 1) ? 1 : 0))) return rc;
       if (go_on && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, true))) return rc;
       if (last && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, false))) return rc;
       // (the last-step records first: a member whose record the other launch writes moves on to its last step)

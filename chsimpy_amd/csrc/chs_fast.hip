@@ -195,9 +195,6 @@ static void select_partial_set(Engine* E) {
   E->dPartE2 = E->partSet[par][2]; E->dPartRa = E->partSet[par][3];
 }
 
-#ifndef CHS_ENTRY_REVERSE
-#define CHS_ENTRY_REVERSE 0
-#endif
 // Entry of a call on the fused pipeline: hat_U <- dctn(U) (solver.py:159) and the prologue below with
 // one sweep of U instead of two (k_row_fwd2), the row transform of U parked in the idle T2 buffer.
 int chs_fast_enter_fused(Engine* E) {
@@ -210,24 +207,24 @@ int chs_fast_enter_fused(Engine* E) {
   chs_slot_end(E, SLOT_MU);
   if (rc) return rc;
   // k_col<FWD_NATIVE> writes hat_U tile by tile in ascending order.  The first step's k_col walks the tiles in ASCENDING
-  // order too (0; 1 = descending: what was written last is read first -- measured 2.3 % slower on a literal 20-step call,
-  // profiles/r04_ab_dma.txt), whatever the parity of the steps of earlier calls; then the directions alternate (CHS_COL_ZIGZAG)
-  if (CHS_ENTRY_REVERSE >= 0) E->stepCount = CHS_ENTRY_REVERSE;
+  // order too (descending -- what was written last is read first -- measured 2.3 % slower on a literal 20-step call,
+  // profiles/r04_ab_dma.txt), whatever the parity of the steps of earlier calls; then the directions alternate
+  E->stepCount = 0;
   return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr);
 }
 
 // Entry of a literal call that finds the first step's operand on the device: the previous call's last step was the fused
 // row kernel (it stored U in full AND left T1 = the row transform of EnergieEut(U) with its sum of squares, exactly what
 // the steps inside a call hand to each other), nothing has touched the field since.  hat_U = dctn(U) is recomputed here,
-// literally (solver.py:159): row pass of U (streamed) into the idle T2 buffer, column pass into hat_U.  What is NOT
+// literally (solver.py:159): row pass of U into the idle T2 buffer, column pass into hat_U.  What is NOT
 // recomputed is EnergieEut(U) and its row transform -- a function of the unchanged U, bit for bit what k_row_fwd2 would
 // produce again.
 int chs_fast_enter_hat(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
   int rc;
-  static const int mode = [] { const char* e = getenv("CHS_ENTRY_HAT_MODE"); return e ? atoi(e) : (int)ROW_FWD_PLAIN; }();   // (cached stores: 86 us; non-temporal ones, ROW_FWD_STREAM: 190-210 us)
-  if ((rc = P->row_fwd(E, E->dU, E->dT2, mode))) return rc;
-  if (CHS_ENTRY_REVERSE >= 0) E->stepCount = CHS_ENTRY_REVERSE;
+  // (ordinary cached stores: this kernel 86 us at N=4096 fp64 against 190-210 us with non-temporal ones, profiles/r04_ab_entry.txt)
+  if ((rc = P->row_fwd(E, E->dU, E->dT2, ROW_FWD_PLAIN))) return rc;
+  E->stepCount = 0;
   return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr);
 }
 
@@ -299,7 +296,7 @@ int chs_fast_step(Engine* E, bool first, bool last) {
   // T2 (columns inverted) overwrites T1 in place: every workgroup of k_col reads exactly the part
   // of the tile it later writes, every workgroup of the fused row kernel likewise for its rows --
   // one array less in the per-step working set (T + hat_U = 268 MB next to a 256 MB Infinity Cache)
-  void* T2 = CHS_ALIAS_T ? E->dT1 : E->dT2;
+  void* T2 = E->dT1;
   if (hat_flip(E)) {
     if (!E->dHat2) CHS_HIP(hipMalloc(&E->dHat2, (size_t)E->N * E->N * E->esz));
     E->hatFlip = true;

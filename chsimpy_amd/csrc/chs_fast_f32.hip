@@ -30,17 +30,11 @@
 // whose staging buffer is as large as its paired scratch, gains nothing from it (split exchanges with the whole pass-0
 // table in LDS: 343 against 316 us; with three workgroups per CU, 140 B of spills: 370-382; 4 columns per 512-thread
 // workgroup, 280 B of spills: 359).
-#ifndef CHS_G8192_XPAIR
-#define CHS_G8192_XPAIR 0
-#endif
-using G8192 = FCfg<float, 8192, 128, 256, 16, 16, 1, 16, 2, 1, 16, CHS_G8192_WPS, CHS_F32_CT, CHS_G8192_XPAIR>;
+using G8192 = FCfg<float, 8192, 128, 256, 16, 16, 1, 16, 2, 1, 16, CHS_G8192_WPS, CHS_F32_CT, 0>;
 #ifndef CHS_G8192C_THREADS
 #define CHS_G8192C_THREADS 256
 #endif
-#ifndef CHS_G8192C_XPAIR
-#define CHS_G8192C_XPAIR -1
-#endif
-using G8192C = FCfg<float, 8192, 128, CHS_G8192C_THREADS, 16, 16, 1, 16, 2, 1, 16, CHS_G8192C_WPS, CHS_F32_CT, CHS_G8192C_XPAIR>;
+using G8192C = FCfg<float, 8192, 128, CHS_G8192C_THREADS, 16, 16, 1, 16, 2, 1, 16, CHS_G8192C_WPS, CHS_F32_CT>;
 template <> struct ColTwLds<G8192C> { static constexpr int value = CHS_G8192C_TW_LDS; };
 #ifndef CHS_G8192_ROW_TW_LDS
 #define CHS_G8192_ROW_TW_LDS 2

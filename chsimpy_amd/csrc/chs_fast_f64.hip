@@ -23,10 +23,7 @@ using F1024 = FCfg<double, 1024, 64, 256, 4, 8, 4, 4, 2, 1, 4, 2>;
 // CUs; the powers alone: no change.  profiles/r03_ab_xpair.txt)
 using F2048 = FCfg<double, 2048, 64, 256, 8, 16, 1, 8, 2, 0, 8, 2>;
 using F2048C = F2048;
-#ifndef CHS_F2048C_LAM_SGPR
-#define CHS_F2048C_LAM_SGPR 0   // (with it: 16 bytes of scratch)
-#endif
-template <> struct ColLamSgpr<F2048C> { static constexpr bool value = (CHS_F2048C_LAM_SGPR != 0); };
+template <> struct ColLamSgpr<F2048C> { static constexpr bool value = false; };   // (with it: 16 bytes of scratch)
 // (the pass twiddles of the row kernel in LDS, which pay from N = 4096 upwards, cost 1 % here: 17.1 k against 17.25 k steps/s)
 // N = 4096: two wavefronts per transform, 16 complex values per lane, four radix passes
 #ifndef CHS_ROW_WPS
@@ -70,34 +67,15 @@ template <> struct RowTwLds<F4096> { static constexpr int value = CHS_F4096_ROW_
 // k_col: CHS_COL_THREADS/128 of the 4 columns of a tile per workgroup
 // (paired 16-byte exchange items -- 27 instead of 39 barriers, 463 instead of 559 LDS instructions, 78 instead of 45 KB
 // of LDS -- measured equal: 4829 against 4829 steps/s over three interleaved rounds, profiles/r03_ab_xpair.txt)
-// CHS_F4096C_E32=1 (experiment, VERDICT round 3 item 1b, unrolled form): one wavefront per column, 32 values per lane, radices
-// 16.8.16 -- two exchanges instead of three, no workgroup barrier inside the passes (wave-local groups), 128-thread workgroups
-#ifndef CHS_F4096C_E32
-#define CHS_F4096C_E32 0
-#endif
-#if CHS_F4096C_E32
-using F4096C = FCfg<double, 4096, 64, 128, 16, 8, 1, 16, CHS_PAD1, CHS_PAD2, CHS_COL_PADL, CHS_COL_WPS, CHS_F4096_CT>;
-#else
 using F4096C = FCfg<double, 4096, 128, CHS_COL_THREADS, 8, 4, 8, 8, CHS_PAD1, CHS_PAD2, CHS_COL_PADL, CHS_COL_WPS, CHS_F4096_CT>;
-#endif
 // pass-0 twiddles: the k = 1 entries in LDS, the others as their powers (tw0_load<POW>): k_col 122-124 -> 119-121 us
 // against the whole table in LDS (profiles/r03_ab_tw2.txt); all from L2: 139 us
 #ifndef CHS_F4096C_TW_LDS
 #define CHS_F4096C_TW_LDS 2
 #endif
 template <> struct ColTwLds<F4096C> { static constexpr int value = CHS_F4096C_TW_LDS; };
-#ifndef CHS_F4096C_LAM_SGPR
-#define CHS_F4096C_LAM_SGPR 1
-#endif
-template <> struct ColLamSgpr<F4096C> { static constexpr bool value = (CHS_F4096C_LAM_SGPR != 0); };
-// Stage-in by LDS-DMA (round 4; chs_fast_kernels.h: DmaStage) in this one-workgroup-per-item kernel -- every piece of
-// both halves of the tile requested at kernel entry, one wait, no staging registers, 32 ds_write_b64 per thread fewer,
-// parity green -- measured 2.8 % SLOWER per step (k_col +5 %), in-process A/B on one box: 0.2201 against 0.2139 ms
-// (profiles/r04_ab_dma.txt).  Off; kept as a switch.
-#ifndef CHS_F4096C_DMA
-#define CHS_F4096C_DMA 0
-#endif
-template <> struct ColDma<F4096C> { static constexpr bool value = (CHS_F4096C_DMA != 0); };
+// (stage-in by LDS-DMA instead of through registers: 2.8 % slower per step, k_col +5 % -- profiles/r04_ab_dma.txt,
+// tools/experiments/lds_dma_stage_in)
 
 // fp64 at N = 8192: the shape of the fp32 configuration of that size (four wavefronts per transform,
 // two rows or two of a tile's four columns per 512-thread workgroup)

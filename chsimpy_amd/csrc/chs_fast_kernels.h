@@ -271,14 +271,6 @@ __device__ __forceinline__ int hat_pair_index(int pbase, int l) {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char chs_dyn_lds[];
 
-// Build knobs that remain (everything else that was tried is recorded with its measurement in DESIGN.md section 7):
-#ifndef CHS_ALIAS_T
-#define CHS_ALIAS_T 1     // T2 overwrites T1 in place (one array less in the per-step working set)
-#endif
-#ifndef CHS_COL_ZIGZAG
-#define CHS_COL_ZIGZAG 1  // k_col walks the tiles in alternating direction from step to step (Infinity Cache)
-#endif
-
 // The fused row kernel takes its pass twiddles from L2 (its four workgroups per CU leave no LDS) unless a configuration
 // has room for the compact form: the k = 1 entries of the pass-0 table + the middle-pass tables, the other pass-0
 // twiddles as powers (tw0_load<POW>)
@@ -406,10 +398,7 @@ __device__ __forceinline__ int launder(int x) {
 // block's sum(mu^2) is recorded (solver.py:225); otherwise a plain transform.
 // (Prologue of a solve_or_resume call, and the unfused/jitter path.)
 // ---------------------------------------------------------------------------
-// STREAM (the row half of hat_U = dctn(U) at the entry of a call that finds the first step's operand already on the
-// device, chs_fast_enter_hat): U is read for the last time and the result is read once, by k_col<FWD_NATIVE> right behind
-// this kernel -- non-temporal stores, as k_row_fwd2's.
-template <class C, bool POINTWISE, bool STREAM = false>
+template <class C, bool POINTWISE>
 __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd(const typename C::T* __restrict__ U, typename C::T* __restrict__ T1,
                                                     FTables<typename C::T> tb, DevConsts dc,
                                                     const DevState* __restrict__ st, double* __restrict__ partMu) {
@@ -435,8 +424,8 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd(const typename C
 #pragma unroll
     for (int j = 0; j < C::R0 / 2; ++j) {
       T q1[4], q2[4];
-      // (ordinary loads also with STREAM: non-temporal loads that miss every cache took this kernel from ~75 to 188 us at
-      // N=4096 fp64 -- k_row_fwd2's non-temporal second read of U hits L2)
+      // (ordinary loads: non-temporal ones that miss every cache took this kernel from ~75 to 188 us at N=4096 fp64 --
+      // k_row_fwd2's non-temporal second read of U hits L2)
       load4<T>(at_boff(U, (urow + 4u * (unsigned)(m1 + C::L1 * j)) * (unsigned)sizeof(T)), q1);
       load4<T>(at_boff(U, (urow + 4u * (unsigned)(m2 + C::L1 * j)) * (unsigned)sizeof(T)), q2);
       pack_quads<C>(q1, q2, q, j, z);
@@ -480,7 +469,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd(const typename C
                             [&](int pbase, const int* idx, Cx<T>& Ya, Cx<T>& Yb, bool live, NoFetch) {
     if (live) {
       const T y[4] = {cx_re(Ya), cx_im(Ya), cx_re(Yb), cx_im(Yb)};
-      row_store<C, STREAM>(T1, rw, pbase, launder(lr), idx, y);
+      row_store<C>(T1, rw, pbase, launder(lr), idx, y);
     }
   }, [](int, const int*, Cx<T>&, Cx<T>&, bool) {});
   if constexpr (POINTWISE) {
@@ -579,10 +568,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
         const T y[4] = {cx_re(Ya), cx_im(Ya), cx_re(Yb), cx_im(Yb)};
         // Ta is read once, by k_col<FWD_NATIVE> right behind this kernel: streamed like U (driver protocol 4471 -> 4533
         // steps/s, profiles/r03_ab_nt.txt); T1 is the first step's operand and stays cached
-#ifndef CHS_FWD2_TA_NT
-#define CHS_FWD2_TA_NT 1
-#endif
-        if (pass == 0) row_store<C, (CHS_FWD2_TA_NT != 0)>(dst, rw, pbase, launder(lr), idx, y);
+        if (pass == 0) row_store<C, true>(dst, rw, pbase, launder(lr), idx, y);
         else row_store<C>(dst, rw, pbase, launder(lr), idx, y);
       }
     }, [](int, const int*, Cx<T>&, Cx<T>&, bool) {});
@@ -604,7 +590,7 @@ struct BatchMember {
   DevConsts dc;
   DevState* st;
   void* T1;   // the step's T operand: k_col in, fused row kernel out
-  void* T2;   // k_col out, k_row_inv in (aliases T1: CHS_ALIAS_T)
+  void* T2;   // k_col out, k_row_inv in (aliases T1: the step works in place)
   void* hat;  // hat_U, updated in place (after a stop: that of the last completed step)
   void* U;
   double* partDiag; double* partMu; double* partRa; double* partE2;
@@ -657,13 +643,10 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
   const double mean_u = st->meanU;  // requested at entry (k_col of this step wrote it), used in the pointwise part
   // reduction table of the table-driven log, behind the exchange scratch (visible after the first barrier)
   double2* ltab = reinterpret_cast<double2*>(chs_dyn_lds + (size_t)C::C * C::SCR * sizeof(T));
-#ifndef CHS_ROW_TABLES_SPLIT
-#define CHS_ROW_TABLES_SPLIT 1
-#endif
   // (SPLIT: the table copies are requested here and stored behind the first phase's loads, below)
   // (measured: N=8192 fp64 +0.9 %, N=4096 fp64 equal, N=4096 fp32 -0.8 %, N=8192 fp32 -5 %: four row workgroups of a CU
   // cover each other's round trips, and the registers held across the first phase cost the fp32 kernels more)
-  constexpr bool SPLIT = (CHS_ROW_TABLES_SPLIT != 0) && RowTwSplit<C>::value && !C::WAVE_LOCAL && sizeof(T) == 8 && C::N >= 8192;
+  constexpr bool SPLIT = RowTwSplit<C>::value && !C::WAVE_LOCAL && sizeof(T) == 8 && C::N >= 8192;
   constexpr bool LOGT = DIAG && sizeof(T) == 8;
   [[maybe_unused]] RowTwSplit<C> tabs;
   if constexpr (SPLIT) {
@@ -691,10 +674,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
   struct RowQuad { T y[4]; };
   // (!FUSE: the lane index goes in through an opaque copy -- the once-per-call kernels otherwise keep a multiple of it
   // alive from the log-table copy at the top and spill it; the fused kernel's code is left as it is)
-#ifndef CHS_ROW_IN_PIPE
-#define CHS_ROW_IN_PIPE 0
-#endif
-  recombine<C, false, true, (CHS_ROW_IN_PIPE != 0)>(z, tb, FUSE ? l : fc_opaque(l), [&](int pbase, const int* idx) {
+  recombine<C, false, true, false>(z, tb, FUSE ? l : fc_opaque(l), [&](int pbase, const int* idx) {
     RowQuad p;
     row_load<C>(T2, row, pbase, l, idx, p.y);
     return p;
@@ -731,10 +711,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
       }
     }
   };
-#ifndef CHS_FUSED_U_NT
-#define CHS_FUSED_U_NT 1
-#endif
-  if (FUSE && store_u && CHS_FUSED_U_NT) put_u(std::true_type{});
+  if (FUSE && store_u) put_u(std::true_type{});
   else if (write_u) put_u(std::false_type{});
   if constexpr (DIAG) {
     // np.gradient edge columns: (U[r,1]-U[r,0]) and (U[r,N-1]-U[r,N-2]) live in lane 0
@@ -882,11 +859,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
     __builtin_amdgcn_sched_barrier(0);
     const int lr = row_l<C>(wv, l), sr = row_sub<C>(wv, sub);
     const int rw = row_of_block<C>(blockIdx.x) + sr;
-#ifndef CHS_ROW_OUT_PIPE
-#define CHS_ROW_OUT_PIPE 0
-#endif
-    // (CHS_ROW_OUT_PIPE: the twiddles of slot k+1 requested in front of slot k's T1 stores, as k_col's spectral stage does)
-    recombine<C, true, false, (CHS_ROW_OUT_PIPE != 0)>(z, tb, lr, [](int, const int*) { return NoFetch{}; },
+    recombine<C, true, false, false>(z, tb, lr, [](int, const int*) { return NoFetch{}; },
                               [](int, const int*, Cx<T>&, Cx<T>&, bool, NoFetch) {},
                               [&](int pbase, const int* idx, Cx<T>& Ya, Cx<T>& Yb, bool live) {
       if (live) {
@@ -915,44 +888,6 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
 // by Parseval this is the interior part of np.gradient's sum of squares (solver.py:
 // 213-217) -- see DESIGN.md section "E2 from the spectrum".
 // ---------------------------------------------------------------------------
-// ---- LDS-DMA stage-in (ColDma): the tile rows go from L2 straight into LDS (global_load_lds_dwordx4: no staging
-// registers, no ds_write), every piece of both halves requested at kernel entry, ONE wait.
-// byte address of an LDS object inside the workgroup's allocation (what DS instructions and M0 take)
-__device__ __forceinline__ unsigned lds_byte_addr(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-// one LDS-DMA piece: 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS at `lds_dst` (wave-uniform).
-// M0 carries the destination; it is compiler-reserved, hence saved and restored inside the statement
-// (cdna_hip_programming.md, inline-assembly rules).
-template <bool NT>
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  if constexpr (NT)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-  else
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// which configurations stage in by LDS-DMA (chs_fast_f64.hip)
-template <class C>
-struct ColDma { static constexpr bool value = false; };
-// Landing-zone image of one half of the tile (N/2 rows): one 16-byte unit per tile row (the workgroup's 2 columns).  A DMA
-// piece writes 1 KiB linearly -- lane i's 16 bytes at base + 16 i -- so the bank spread that the padded image of the
-// register path gets from its pitch comes from permuting the rows INSIDE each quad on the SOURCE side: unit 4m + (e ^
-// ((m >> 2) & 3)) holds row 4m + e.  The lanes of a piece still fetch the same 16 lines (coalescing unchanged); the quad
-// reads are 2-way conflicted at worst (lanes i and i+16: 32 lanes x 8 bytes out of 16-byte units reach half the banks).
-template <class C>
-struct DmaStage {
-  static constexpr int ROWS = C::N / 2;
-  static constexpr int NW = C::THREADS / 64;
-  static constexpr int NDMA = ROWS / (64 * NW);   // pieces per wavefront and half
-  static constexpr int ZONE = ROWS * C::C;         // elements of a landing zone
-  static constexpr bool OK = (C::C * sizeof(typename C::T) == 16) && (C::G % 64 == 0) && (ROWS % (64 * NW) == 0) && (C::R0 >= 4);
-  static __device__ __forceinline__ int row_of_unit(int p) { const int mq = p >> 2; return 4 * mq + ((p & 3) ^ ((mq >> 2) & 3)); }
-  static __device__ __forceinline__ int unit_of(int mm, int e) { return 4 * mm + (e ^ ((mm >> 2) & 3)); }
-};
-
 template <class C>
 struct ColStage {
   // A workgroup stages C of the CT columns of a tile: per row a piece of C elements at offset
@@ -993,18 +928,6 @@ struct ColLamSgpr { static constexpr bool value = true; };
 // ... and whether the tile workgroups start with their loads (stop flag taken along with the first staging barrier, twiddle
 // copy requested in front of the first tile request and stored behind it) instead of two L2 round trips and a barrier in
 // front of them: where the extra registers held across the request do not spill (fp64 below N = 4096: 48-80 bytes)
-#ifndef CHS_COL_PIPE
-#define CHS_COL_PIPE 1   // 0: the spectral stage fetches slot k in slot k (fewer live registers; measured)
-#endif
-#ifndef CHS_COL_PRE0
-#define CHS_COL_PRE0 0   // (measured: fp32 within +-0.5 %, fp64 -- with the coefficients left in VGPRs to avoid scratch -- 2.4 % slower)
-#endif
-#ifndef CHS_COL_PRE0_F64
-#define CHS_COL_PRE0_F64 0   // (fp64 at its 256 registers: 20-28 bytes of scratch with it, unless the coefficients stay in VGPRs)
-#endif
-// ... and whether the spectral stage's first request goes out in front of the last forward pass (k_col: PRE0)
-template <class C>
-struct ColPre0 { static constexpr bool value = (CHS_COL_PRE0 != 0) && (sizeof(typename C::T) == 4 || (CHS_COL_PRE0_F64 != 0 && C::N >= 4096)); };
 template <class C>
 struct ColLateStart { static constexpr bool value = (sizeof(typename C::T) == 4) || (C::N >= 4096); };
 template <class C>
@@ -1016,9 +939,7 @@ constexpr int col_tw_lds_elems() {
 
 template <class C>
 constexpr int col_lds_elems() {
-  constexpr int base = (C::C * C::SCR > ColStage<C>::ELEMS) ? C::C * C::SCR : ColStage<C>::ELEMS;
-  // (LDS-DMA stage-in: the two landing zones, which the exchange scratch and the stage-out image then reuse)
-  return (ColDma<C>::value && 2 * DmaStage<C>::ZONE > base) ? 2 * DmaStage<C>::ZONE : base;
+  return (C::C * C::SCR > ColStage<C>::ELEMS) ? C::C * C::SCR : ColStage<C>::ELEMS;
 }
 
 template <class C, int MODE, class... Batch>
@@ -1034,18 +955,16 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
     static_assert(MODE == MODE_STEP, "batches launch the step's column pass only");
     ConstBatchMember& m = batch_member(mem...);
     if (m.st->rows_written >= m.nsteps) return;
-    Tin = (const T*)m.T1; Tout = CHS_ALIAS_T ? (T*)m.T1 : (T*)m.T2; hat = (T*)m.hat; st = m.st; partE2 = m.partE2;
+    Tin = (const T*)m.T1; Tout = (T*)m.T1; hat = (T*)m.hat; st = m.st; partE2 = m.partE2;
   }
   __shared__ double red[32];
   // MODE_STEP: block 0 of this very launch may raise the stop flag (the riding tail, a gate that timed out): one thread
-  // reads it for the whole workgroup, so that all its wavefronts leave or stay together.  EARLY_HALT: at the very top, in
-  // front of everything (a load, a barrier and an LDS round trip before the first tile load is even requested); otherwise
-  // the tile workgroups take the flag along with their first staging barrier -- nothing but loads has been issued by then.
+  // reads it for the whole workgroup, so that all its wavefronts leave or stay together.  !LATE_HALT: at the very top, in
+  // front of everything (a load, a barrier and an LDS round trip before the first tile load is even requested); LATE_HALT
+  // (ColLateStart): the tile workgroups take the flag along with their first staging barrier -- nothing but loads has been
+  // issued by then.
   __shared__ int halted;
-#ifndef CHS_COL_LATE_HALT
-#define CHS_COL_LATE_HALT 1
-#endif
-  constexpr bool LATE_HALT = (MODE == MODE_STEP) && (CHS_COL_LATE_HALT != 0) && ColLateStart<C>::value && !(ColDma<C>::value);
+  constexpr bool LATE_HALT = (MODE == MODE_STEP) && ColLateStart<C>::value;
   if constexpr (MODE == MODE_STEP && !LATE_HALT) {
     if (threadIdx.x == 0) halted = st->halt;
     __syncthreads();
@@ -1101,10 +1020,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
   // wait behind the hat_U stores at the start of the inverse passes
   FTables<T> tbp = tb;
   constexpr bool TW0POW = (MODE == MODE_STEP) && (ColTwLds<C>::value == 2);
-  constexpr bool DMA = ColDma<C>::value && (MODE == MODE_STEP || MODE == MODE_FWD_NATIVE);
-  static_assert(!DMA || (DmaStage<C>::OK && sizeof(T) == 8), "LDS-DMA stage-in: 16-byte row pieces of whole wavefronts");
-  // (DMA: the twiddle copy is requested in front of the DMA pieces and stored behind their wait, below)
-  // LATE_HALT (the register-staged path): the copy's loads are requested HERE and stored to LDS behind the request of
+  // LATE_HALT: the copy's loads are requested HERE and stored to LDS behind the request of
   // the first half of the tile -- as a load/store loop in front of it, the copy was two L2 round trips in a row during
   // which no tile load was in flight (~1.5 K cycles of a ~47 K-cycle workgroup life)
   constexpr bool TW_SPLIT = LATE_HALT && (ColTwLds<C>::value != 0);
@@ -1129,7 +1045,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
     tbp.twa = ltw + TW_N0;
     tbp.twb = tbp.twa + (C::RA > 1 ? 2 * (C::RA - 1) * C::L2 : 0);
   }
-  if constexpr (MODE == MODE_STEP && ColTwLds<C>::value != 0 && !DMA && !TW_SPLIT) {
+  if constexpr (MODE == MODE_STEP && ColTwLds<C>::value != 0 && !TW_SPLIT) {
     T* ltw = lds + col_lds_elems<C>();
     // pass-0 part (the whole table, or its k = 1 entries), then twa | twb (contiguous behind tw0 in the table buffer)
     constexpr int N0 = TW0POW ? 2 * C::L1 : 2 * (C::R0 - 1) * C::L1;
@@ -1184,101 +1100,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
     p.h23 = ldc_hint<T, HAT_NT_LD>(hcol, hp + C::G);
     return p;
   };
-  // The spectral stage's first request (slot 0 of pair 0: twiddles, hat_U, eigenvalues) goes out in front of the LAST forward
-  // pass instead of behind it: its round trip (hat_U comes from the Infinity Cache) runs under that pass's butterflies
-  // (ColPre0; where a lane owns one pair, E = 2 RL, and the stage is pipelined)
-  constexpr bool PRE0 = (MODE == MODE_STEP) && ColPre0<C>::value && !DMA && !PreAll<C>::value && (CHS_COL_PIPE != 0) && (C::NP2 == 1);
-  // (hat_U alone: it is what comes from furthest away; the whole request held across the pass spilled 20-40 bytes in fp64)
-  struct HatPre {
-    Cx<T> h01, h23;
-    __device__ __forceinline__ void patch(Fetched& p) const { p.h01 = h01; p.h23 = h23; }
-  };
-  [[maybe_unused]] HatPre s0;
-  if constexpr (DMA) {
-    // ---- stage in by LDS-DMA: all pieces of both halves of the tile (NDMA per wavefront and half) are requested here,
-    // in front of them the (compiler-visible) loads of the pass twiddles; one wait covers everything (vector-memory
-    // operations complete in order), then the twiddles go to LDS, one barrier, and every lane reads its quads.
-    using DS = DmaStage<C>;
-    constexpr bool TWL = (MODE == MODE_STEP && ColTwLds<C>::value != 0);
-    constexpr int N0 = TW0POW ? 2 * C::L1 : 2 * (C::R0 - 1) * C::L1;
-    constexpr int NM = col_tw_lds_elems<C>() - N0;
-    constexpr int TWI0 = (N0 + 2 * C::THREADS - 1) / (2 * C::THREADS), TWIM = (NM + 2 * C::THREADS - 1) / (2 * C::THREADS);
-    [[maybe_unused]] double2 tw_a[TWL ? TWI0 : 1], tw_b[TWL ? TWIM : 1];
-    T* ltw = lds + col_lds_elems<C>();
-    if constexpr (TWL) {
-#pragma unroll
-      for (int i = 0; i < TWI0; ++i) {
-        const int e = 2 * ((int)threadIdx.x + i * C::THREADS);
-        if (e < N0) tw_a[i] = *reinterpret_cast<const double2*>(tb.tw0 + e);
-      }
-#pragma unroll
-      for (int i = 0; i < TWIM; ++i) {
-        const int e = 2 * ((int)threadIdx.x + i * C::THREADS);
-        if (e < NM) tw_b[i] = *reinterpret_cast<const double2*>(tb.twa + e);
-      }
-      tbp.tw0 = ltw;
-      tbp.twa = ltw + N0;
-      tbp.twb = tbp.twa + (C::RA > 1 ? 2 * (C::RA - 1) * C::L2 : 0);
-    }
-    {
-      const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-      const T* tile = Tin + (size_t)ct * C::N * C::CT + hh * C::C;
-      const unsigned base = lds_byte_addr(lds);
-      constexpr bool NT = (MODE == MODE_FWD_NATIVE);  // the entry's intermediate (k_row_fwd2's Ta): its only read
-#pragma unroll
-      for (int rho = 0; rho < 2; ++rho) {
-#pragma unroll
-        for (int i = 0; i < DS::NDMA; ++i) {
-          const int piece = i * DS::NW + wave;
-          const int row = rho * DS::ROWS + DS::row_of_unit(piece * 64 + lane);
-          glds16<NT>(tile + (size_t)row * C::CT,
-                     __builtin_amdgcn_readfirstlane(base + (unsigned)((rho * DS::ZONE) * sizeof(T)) + piece * 1024));
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (TWL) {
-#pragma unroll
-      for (int i = 0; i < TWI0; ++i) {
-        const int e = 2 * ((int)threadIdx.x + i * C::THREADS);
-        if (e < N0) *reinterpret_cast<double2*>(ltw + e) = tw_a[i];
-      }
-#pragma unroll
-      for (int i = 0; i < TWIM; ++i) {
-        const int e = 2 * ((int)threadIdx.x + i * C::THREADS);
-        if (e < NM) *reinterpret_cast<double2*>(ltw + N0 + e) = tw_b[i];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int rho = 0; rho < 2; ++rho) {
-      const T* zone = lds + rho * DS::ZONE;
-#pragma unroll
-      for (int q = 0; q < C::NP0; ++q) {
-        const int m1 = l + C::G * q, m2 = C::L1 - 1 - m1;
-#pragma unroll
-        for (int jj = 0; jj < CS::JR; ++jj) {
-          const int j = rho * CS::JR + jj;
-          T q1[4], q2[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            q1[e] = zone[DS::unit_of(m1 + C::L1 * jj, e) * C::C + sub];
-            q2[e] = zone[DS::unit_of(m2 + C::L1 * jj, e) * C::C + sub];
-          }
-          pack_quads<C>(q1, q2, q, j, z);
-        }
-      }
-    }
-    __syncthreads();   // the landing zones become the exchange scratch
-    if constexpr (MODE == MODE_STEP) STAMP(1, 1);
-    fwd_passes<C, TW0POW>(z, scr, tbp, l);
-    if constexpr (MODE == MODE_STEP) STAMP(1, 2);
-    if constexpr (MODE == MODE_STEP) {
-      if (ta.gate) {  // (the gated tail: see the register-staged path below)
-        if (gate_wait(st, ta.seq, ta.gate_spins, red, lam1, lam2)) return;
-      }
-    }
-  } else if constexpr (MODE != MODE_INV_NATURAL && MODE != MODE_INV_NATIVE) {
+  if constexpr (MODE != MODE_INV_NATURAL && MODE != MODE_INV_NATIVE) {
     // ---- stage in: tile rows -> quads of this group's column.  The first half is requested at once, the
     // second as soon as the first has left its registers (its latency runs under the first half's barrier
     // and quad reads); both pass through LDS half by half.
@@ -1366,20 +1188,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
     }
     __syncthreads();
     if constexpr (MODE == MODE_STEP) STAMP(1, 1);
-#ifndef CHS_GATE_EARLY_POLL
-#define CHS_GATE_EARLY_POLL 0   // (measured equal in energy-stop mode: 0.9932 / 0.9954 with it off; experiment switch)
-#endif
-    // (gated launches: the polling lane asks for the sequence word HERE; the answer is looked at behind the passes)
-    [[maybe_unused]] unsigned long long early_seq = ~0ull;
-    if constexpr (MODE == MODE_STEP && CHS_GATE_EARLY_POLL != 0) {
-      if (ta.gate && threadIdx.x == 0) early_seq = __hip_atomic_load(&st->decided, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if constexpr (PRE0) fwd_passes<C, TW0POW>(z, scr, tbp, l, [&]() {
-      const int hp = hat_pair_index<C>(0, fc_opaque(l));
-      s0.h01 = ldc_hint<T, HAT_NT_LD>(hcol, hp);
-      s0.h23 = ldc_hint<T, HAT_NT_LD>(hcol, hp + C::G);
-    });
-    else fwd_passes<C, TW0POW>(z, scr, tbp, l);
+    fwd_passes<C, TW0POW>(z, scr, tbp, l);
     if constexpr (MODE == MODE_STEP) STAMP(1, 2);
     if constexpr (MODE == MODE_STEP) {
       // Gated tail: the bookkeeping of the previous step -- stop rules, adaptive time step -- runs as block 0
@@ -1387,17 +1196,14 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
       // decision here: stopped -> leave hat_U, T and the partial sums as the previous step left them
       // (run_steps rebuilds U from hat_U); otherwise take this step's coefficients from it.
       if (ta.gate) {
-        if (gate_wait(st, ta.seq, ta.gate_spins, red, lam1, lam2, early_seq)) return;
+        if (gate_wait(st, ta.seq, ta.gate_spins, red, lam1, lam2)) return;
       }
     }
   }
 
   // ---- recombination / spectral stage / adjoint recombination, in place per slot
   double e2 = 0.0;
-#ifndef CHS_MEAN_NOW_ALL
-#define CHS_MEAN_NOW_ALL 0
-#endif
-  constexpr bool MEAN_NOW = !PreAll<C>::value || (CHS_MEAN_NOW_ALL != 0);
+  constexpr bool MEAN_NOW = !PreAll<C>::value;
   [[maybe_unused]] T h00 = T(0);
   constexpr bool FWD = (MODE != MODE_INV_NATURAL && MODE != MODE_INV_NATIVE);
   constexpr bool ADJ = (MODE == MODE_STEP || MODE == MODE_INV_NATURAL || MODE == MODE_INV_NATIVE);
@@ -1467,8 +1273,9 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
           stc_hint<T, HAT_NT_ST>(hout, hp + C::G, Yb);
         }
       };
-    if constexpr (PRE0) recombine<C, true, true, (CHS_COL_PIPE != 0)>(z, tb, l, fetch, spec_f, spec_st, &s0);
-    else recombine<C, true, true, (CHS_COL_PIPE != 0)>(z, tb, l, fetch, spec_f, spec_st);
+    // (pipelined -- slot k+1 requested in front of slot k's stores; slot k fetched in slot k keeps
+    // fewer registers live and measured within +-1 %, section 7)
+    recombine<C, true, true, true>(z, tb, l, fetch, spec_f, spec_st);
     if constexpr (sizeof(T) == 4) e2 = (double)e2v.x + (double)e2v.y;
   } else {
     recombine<C, FWD, ADJ, false>(z, tb, l, [](int, const int*) { return NoFetch{}; },
@@ -1536,15 +1343,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
           *reinterpret_cast<chs_f4v*>(dst) = v;
         } else {
           const T a = lds[lo], b = lds[lo + 1];
-#ifndef CHS_COL_OUT_POLICY
-#define CHS_COL_OUT_POLICY 0   // experiment: cache policy of k_col's T stores: 0 plain, 1 sc1 (write-through), 2 nt, 3 sc0 sc1
-#endif
-          if constexpr (sizeof(T) == 8 && CHS_COL_OUT_POLICY != 0 && MODE == MODE_STEP) {
-            chs_d2v v; v.x = a; v.y = b;
-            if constexpr (CHS_COL_OUT_POLICY == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst), "v"(v) : "memory");
-            else if constexpr (CHS_COL_OUT_POLICY == 2) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(dst), "v"(v) : "memory");
-            else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(v) : "memory");
-          } else if constexpr (sizeof(T) == 8) *reinterpret_cast<double2*>(dst) = make_double2(a, b);
+          if constexpr (sizeof(T) == 8) *reinterpret_cast<double2*>(dst) = make_double2(a, b);
           else *reinterpret_cast<float2*>(dst) = make_float2(a, b);
         }
       }
@@ -1563,13 +1362,13 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
 // host side
 // ---------------------------------------------------------------------------
 enum { ROW_INV_PLAIN = 0, ROW_INV_DIAG = 1, ROW_INV_FUSED = 2, ROW_INV_FUSED_ADAPT = 3 };
-enum { ROW_FWD_PLAIN = 0, ROW_FWD_POINTWISE = 1, ROW_FWD_STREAM = 2 };
+enum { ROW_FWD_PLAIN = 0, ROW_FWD_POINTWISE = 1 };
 
 struct FastPlan {
   int N, G, R0, RA, RB, RL, threads, col_tiles;
   void* tables = nullptr;  // one device allocation
   size_t off_tw0, off_twa, off_twb, off_wp, off_t1, off_t2, off_lam4 = 0, off_sin4 = 0;  // element offsets
-  int (*row_fwd)(Engine*, const void*, void*, int) = nullptr;   // mode: ROW_FWD_PLAIN / _POINTWISE / _STREAM
+  int (*row_fwd)(Engine*, const void*, void*, int) = nullptr;   // mode: ROW_FWD_PLAIN / _POINTWISE
   int (*row_fwd2)(Engine*, const void*, void*, void*) = nullptr;
   int (*row_inv)(Engine*, int, const void*, void*, void*) = nullptr;
   int (*col)(Engine*, int, const void*, void*, void*, void*) = nullptr;
@@ -1613,7 +1412,6 @@ struct Launch {
     int rc;
     if ((rc = set_lds(k_row_fwd<C, true>, row_lds))) return rc;
     if ((rc = set_lds(k_row_fwd<C, false>, row_lds))) return rc;
-    if ((rc = set_lds(k_row_fwd<C, false, true>, row_lds))) return rc;
     if ((rc = set_lds(k_row_fwd2<C>, row_lds))) return rc;
     if ((rc = set_lds(k_row_inv<C, false, false>, row_lds))) return rc;
     if ((rc = set_lds(k_row_inv<C, true, false>, row_lds))) return rc;
@@ -1622,7 +1420,6 @@ struct Launch {
       if ((rc = set_lds(k_row_inv<C, true, true, true>, row_lds))) return rc;
     }
     E->adaptOk = ADAPT_OK;
-    E->fusedAdapt = ADAPT_OK && getenv("CHS_ADAPT_SWEEP") == nullptr;  // CHS_ADAPT_SWEEP=1: keep the separate sweep of U
     if ((rc = set_lds(k_col<CC, MODE_STEP>, col_lds))) return rc;
     if ((rc = set_lds(k_col<CC, MODE_FWD_NATIVE>, col_lds))) return rc;
     if ((rc = set_lds(k_col<CC, MODE_FWD_NATURAL>, col_lds))) return rc;
@@ -1635,9 +1432,6 @@ struct Launch {
     if (mode == ROW_FWD_POINTWISE)
       k_row_fwd<C, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)in, (T*)out, get_tables<T>(E), E->dc, E->dState,
                                                             E->dPartMu);
-    else if (mode == ROW_FWD_STREAM)
-      k_row_fwd<C, false, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)in, (T*)out, get_tables<T>(E), E->dc, E->dState,
-                                                                   E->dPartMu);
     else
       k_row_fwd<C, false><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)in, (T*)out, get_tables<T>(E), E->dc, E->dState,
                                                              E->dPartMu);
@@ -1692,7 +1486,7 @@ struct Launch {
           g = grid + 1;
         }
         E->preRider = false;
-        ta.reverse = (CHS_COL_ZIGZAG && (E->stepCount & 1)) ? 1 : 0;
+        ta.reverse = (E->stepCount & 1) ? 1 : 0;
         ++E->stepCount;
         k_col<CC, MODE_STEP><<<g, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
         break;

@@ -148,12 +148,8 @@ __device__ __forceinline__ double chs_log_unit_tab_f64(double x, const double2* 
 // fp32 engine: x = U, 1-U or their quotient, never denormal: the hardware log2 (1 ulp) times ln 2 instead of the
 // library's range-checked sequence (~10 instructions per logarithm); log of a non-positive number gives NaN / -inf
 // as the library's does.  Every fp32 path uses the same function (the fused kernels and the sweep kernels agree).
-#ifndef CHS_F32_NATIVE_LOG
-#define CHS_F32_NATIVE_LOG 1
-#endif
 __device__ __forceinline__ float chs_logf(float x) {
-  if constexpr (CHS_F32_NATIVE_LOG != 0) return __builtin_amdgcn_logf(x) * 0.69314718055994530942f;
-  return logf(x);
+  return __builtin_amdgcn_logf(x) * 0.69314718055994530942f;
 }
 template <typename T> __device__ __forceinline__ T chs_log_pos(T x);
 template <> __device__ __forceinline__ double chs_log_pos<double>(double x) { return chs_log_pos_f64(x); }
@@ -290,18 +286,10 @@ __device__ __forceinline__ T chs_spectral(T hatU, T hatMu, double li, double lj,
 #pragma clang fp contract(off)
   if constexpr (sizeof(T) == 4 && F32MATH) return chs_spectral_f32(hatU, hatMu, li, lj, lam1, lam2);
   const double leig = li + lj;
-#ifndef CHS_SPECTRAL_FMA
-#define CHS_SPECTRAL_FMA 0
-#endif
-#if CHS_SPECTRAL_FMA
-  // fused multiply-adds (one rounding less each than numpy's separate operations: differences of an ulp in hat_U)
-  const double CHeig = __builtin_fma(lam2 * leig, leig, 1.0);
-  const double rhs = __builtin_fma(lam1 * leig, (double)hatMu, (double)hatU);
-#else
+  // (numpy's separate operations, no fused multiply-adds: those differ by an ulp in hat_U)
   const double CHeig = 1.0 + (lam2 * leig) * leig;
   const double Seig = lam1 * leig;
   const double rhs = (double)hatU + Seig * (double)hatMu;
-#endif
   // CHeig >= 1: reciprocal + one Newton step + residual correction (the correction squares the
   // reciprocal's remaining error: < 1 ulp of the correctly rounded quotient, measured) instead of the
   // ~2.5x longer IEEE division sequence

@@ -292,8 +292,10 @@ __device__ __forceinline__ void step_tail_body(const TailArgs& ta, DevState* __r
 // drained them, released at agent scope and then stored the sequence number.  The consumer's polling lane polls
 // relaxed, issues ONE agent-scope acquire once the poll has matched and then reads the payload itself (agent-scope
 // loads); the other wavefronts get the values through LDS behind the workgroup barrier.  `box` = 4 doubles of LDS.
-// `early` = what the polling lane read from the sequence word in front of the forward passes (a load whose round trip ran under
-// them): when it already shows this launch's number -- every workgroup but those of the first round -- no poll is needed at all.
+// (`early`: a value of the sequence word read ahead of the call spares the poll when it matches.  Reading it in front of
+// the forward passes measured equal, profiles/r04_ab_rows.txt, and no caller passes it now; the parameter and its compare
+// stay because k_col<MODE_STEP> compiles to other code without them, and with the early publication of the adaptive
+// step's coefficients -- TailArgs::early, CHS_GATE_EARLY -- they go in a change that is measured on the GPU.)
 __device__ __forceinline__ int gate_wait(DevState* __restrict__ st, unsigned long long seq, int spins, double* box,
                                          double& lam1, double& lam2, unsigned long long early = ~0ull) {
   if (threadIdx.x == 0) {
@@ -311,14 +313,7 @@ __device__ __forceinline__ int gate_wait(DevState* __restrict__ st, unsigned lon
     // ONE agent-scope acquire in the polling lane, once per workgroup and step, behind the matched poll: the payload
     // loads below are ordered behind the poll by the memory model, not by what gfx950 happens to do with sc1 loads
     // (gated modes only -- stop rules armed or an adaptive step)
-#ifndef CHS_GATE_ACQUIRE
-#define CHS_GATE_ACQUIRE 1
-#endif
-#if CHS_GATE_ACQUIRE
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
-    asm volatile("" ::: "memory");
-#endif
     const int halt = __hip_atomic_load(&st->halt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     box[0] = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(&st->lam1), __ATOMIC_RELAXED,
                                                                __HIP_MEMORY_SCOPE_AGENT));

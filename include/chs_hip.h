@@ -97,7 +97,11 @@ typedef struct chs_handle_s* chs_handle;
  * the fly from this table and the current delt.
  * Environment (read here, test hooks): CHS_ADAPT_SWEEP=1 keeps the separate sweep
  * of U for the adaptive-step column sums instead of the fused row kernel's;
- * CHS_BATCH_STEPS=n issues the steps of a call n at a time (default 1024) -- between
+ * CHS_ADAPT_SPARSE=0 issues the adaptive step's reduction launches and the gate on every step instead of only on
+ * the steps whose step-size rule fires; CHS_LAM_BY_COLMIN=0 leaves the coefficients of a firing step to the gated
+ * bookkeeping instead of the reduction's last block; CHS_GATE_EARLY=1 (experiment, measured equal) lets that
+ * bookkeeping publish the coefficients ahead of the step's record;
+ * CHS_BATCH_STEPS=n issues the steps of a call n at a time (default 1024, 256 with a stop rule armed) -- between
  * batches the host looks at the device's stop flag, see chs_step_n.
  * chs_destroy parks up to four engines (fields up to 160 MB) instead of freeing them and chs_create takes a
  * parked engine of the same device, N, dtype, transform engine and lambda table into use again with the new

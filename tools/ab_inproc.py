@@ -50,7 +50,7 @@ def main():
     ap.add_argument('--mode', default='continue', choices=['literal', 'continue', 'adaptive', 'estop'])
     ap.add_argument('--delt-max', type=float, default=None)
     ap.add_argument('--glob', default='*')
-    ap.add_argument('--envs', default='', help="';'-separated environment settings, each 'K=V[,K=V]': every variant gets one engine per setting (set while the engine is created), e.g. 'CHS_SLAB=0;CHS_SLAB=1'")
+    ap.add_argument('--envs', default='', help="';'-separated environment settings, each 'K=V[,K=V]': every variant gets one engine per setting (set while the engine is created), e.g. 'CHS_LAM_BY_COLMIN=0;CHS_LAM_BY_COLMIN=1'")
     ap.add_argument('--copies', type=int, default=1, help='engines per variant, created interleaved (a b c a b c ...): where an engine\'s buffers land in memory is worth up to ~1.2 %% between IDENTICAL libraries; several engines per variant average that out')
     ap.add_argument('--reverse', action='store_true', help='create the engines in reverse order (buffer placement differs by engine: a ratio that flips with the order is placement, not code)')
     ap.add_argument('--profile', type=int, default=0, help='afterwards: per-kernel device time (HIP events) over this many steps, per variant')
