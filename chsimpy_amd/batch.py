@@ -7,8 +7,9 @@ members (``chs_batch_*`` of ``include/chs_hip.h``), so that the members' chains 
 Member by member a ``BatchSolver`` is a ``Solver`` with ``rederive_hat=True``: same constants, start field, records,
 stop rules and quirks (the first ``solve_or_resume`` after ``prepare`` runs ``nsteps-1`` iterations; ``prepare`` does
 not reset ``delt`` / ``time_delta_sum`` / ``skip_check``), every call a literal ``solve_or_resume`` of the reference.
-Its scope: the fast engine, N in {128, 256, 512, 1024, 2048}, one dtype and device for all members, a fixed time step
-and no jitter; anything else raises ``ValueError`` before the device is touched.
+Its scope: the fast engine, N in {128, 256, 512, 1024, 2048}, one dtype and device for all members, no jitter, and
+``adaptive_time`` set in all members or in none (an adaptive batch: every member adapts its step by its own rule,
+step counter and ``delt_max``); anything else raises ``ValueError`` before the device is touched.
 
     bs = BatchSolver([params_0, params_1, ...])
     bs.prepare()
@@ -30,8 +31,6 @@ def scope_error(params):
         return f"engine={params.engine!r}: a batch runs the fast engine only"
     if str(getattr(params, 'dtype', 'float64')) not in _lib.DTYPES:
         return f"dtype={params.dtype!r} is not supported"
-    if params.adaptive_time:
-        return "adaptive_time: a batch takes a fixed time step only"
     if params.jitter is not None and 0.0 < params.jitter < 0.1:
         return "jitter: a batch has no per-step noise"
     return None
@@ -49,6 +48,11 @@ def validate(params_list):
         why = scope_error(p)
         if why:
             raise ValueError(f"member {i}: {why}")
+    a0 = bool(params_list[0].adaptive_time)
+    for i, p in enumerate(params_list):
+        if bool(p.adaptive_time) != a0:
+            raise ValueError(f"member {i}: adaptive_time={bool(p.adaptive_time)} differs from member 0's "
+                             f"(a batch adapts the step of all its members or of none)")
     k0 = _key(params_list[0])
     for i, p in enumerate(params_list):
         if _key(p) != k0:

@@ -11,6 +11,15 @@
 // in stream order: the tail of every member runs right behind its row kernel (no riding, no gate, no second hat_U
 // buffer -- what those hide, the launch latency of one member's short kernels, is covered here by the other
 // members' workgroups).  Every kernel body is the single handle's (the tail with the block size it has there).
+//
+// A batch whose members ALL adapt their time step (solver.py:177-193) runs the row kernel that also writes the partial
+// column sums of the step-size integrand (k_row_inv<ADAPT>) and, between the row kernels and the tails,
+//   k_colsum_slices_batch, k_colmin_slices_batch   (chs_pointwise.hip)
+// which reduce every member's partial rows to its column minimum in the single handle's order; the tail of a member
+// whose rule fires reads it (TailArgs::partColMin).  Whether the rule fires is each member's own affair, decided on
+// the device from its own step counter; the host follows the counters (Engine::csHost) only to leave the reduction
+// out on steps where it knows that no running member fires.  A configuration without the fused adaptive row kernel
+// (N = 128: eight rows per workgroup) takes the sums from a sweep of U as its single handle does, member by member.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -91,7 +100,8 @@ extern "C" int chs_batch_create(const chs_consts* consts, int32_t B, const doubl
     if (!batch_n_ok(c.N)) return bad(who + "a batch needs N in {128, 256, 512, 1024, 2048}");
     if (c.engine == CHS_ENGINE_DIRECT) return bad(who + "a batch runs the fast engine only (engine=direct given)");
     if (c.engine != CHS_ENGINE_AUTO && c.engine != CHS_ENGINE_FAST) return bad(who + "bad engine");
-    if (c.adaptive_time) return bad(who + "a batch takes a fixed time step only (adaptive_time given)");
+    if ((c.adaptive_time != 0) != (c0.adaptive_time != 0))
+      return bad(who + "adaptive_time differs from member 0's (a batch adapts the step of all its members or of none)");
   }
   Batch* b = new (std::nothrow) Batch();
   if (!b) return bad("out of host memory");
@@ -216,6 +226,15 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
   CHS_HIP(hipSetDevice(b->device));
   int rc;
   int batch_steps = 1024;
+  // an adaptive batch (all members or none: chs_batch_create); `fused`: the row kernel adds up the step-size integrand
+  bool adaptive = false, fused = true;
+  for (int i = 0; i < B; ++i) {
+    const Engine* E = b->m[i];
+    adaptive |= E->dc.adaptive_time != 0;
+    fused &= E->fusedAdapt && E->dPartColRows != nullptr;
+  }
+  fused &= adaptive;
+  std::vector<long long> cs0((size_t)B, -1);   // the members' step counters at the entry, where the host knows them
   // entry of every member that runs: re-armed loop, hat_U = dctn(U) and the first step's row transform of EnergieEut(U)
   for (int i = 0; i < B; ++i) {
     Engine* E = b->m[i];
@@ -229,7 +248,8 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     if (n == 0) continue;   // sits the call out: state and field stay as they are
     E->stateCached = false; E->resident = false; E->keepResident = false;
     E->tailDeferred = false; E->tailGated = false; E->preRider = false;
-    E->storeU = false;
+    E->storeU = adaptive && !fused;   // (the sweep of U needs the field of every step: chs_fast_step)
+    cs0[(size_t)i] = E->csHost;
     if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) batch_steps = E->batchSteps < batch_steps ? E->batchSteps : batch_steps;
     if ((rc = chs_launch_call_begin(E))) return rc;
     if ((rc = chs_fast_enter_fused(E))) return rc;   // (selects the partial-sum set the whole call uses)
@@ -244,6 +264,13 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     r.tail[0].pre_only = 1;
     r.tail[1] = chs_tail_args(E, -1, 1);
     r.tail[2] = chs_tail_args(E, -1, 0);
+    if (adaptive) {
+      // the first step's time-step control as the single handle runs it: the integrand's column sums from a sweep of
+      // U (the rule looks at the counter as the previous call left it), then k_pre -- once per call
+      if (fused && (rc = chs_colmin_batch_buffers(E, &r))) return rc;
+      if ((rc = chs_launch_mu_colsums(E, 0))) return rc;
+      if ((rc = chs_launch_pre(E))) return rc;
+    }
   }
   if (const char* bs = getenv("CHS_BATCH_STEPS")) {   // (the test hook of chs_step_n: small batches exercise the polls)
     const long v = atol(bs);
@@ -253,9 +280,18 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
   Engine* E0 = b->m[0];
   FastPlan* P = (FastPlan*)E0->dTw;
   std::vector<int64_t> copied((size_t)B, 0);
-  if (maxn > 0) {
+  if (maxn > 0 && !adaptive) {
     if ((rc = launch_tail(b->stream, b->dMem, B, P->col_threads, false, 1))) return rc;
   }
+  // does member i's step-size rule fire behind step s of this call?  (as far as the host can tell: an unknown counter fires)
+  auto fires = [&](int i, int64_t s) {
+    if (s >= nsteps[i] - 1) return false;           // no step behind s: no time-step control
+    if (cs0[(size_t)i] < 0) return true;
+    const long long cs_next = cs0[(size_t)i] + s + 1;   // (chs_tail.h: cs_next; a halted member's kernels are no-ops)
+    return cs_next > 500 && (cs_next % 2) == 0;
+  };
+  const int fuse_mode = fused ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED;
+  const int store_u = (adaptive && !fused) ? 1 : 0;
   int64_t issued = 0;
   int poll = 0;
   bool stopped = false;
@@ -269,8 +305,19 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
         last |= s == nsteps[i] - 1;
       }
       if ((rc = P->col_batch(E0, b->stream, b->dMem, B, (s & 1) ? 1 : 0))) return rc;
-      if (go_on && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, true))) return rc;
-      if (last && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, false))) return rc;
+      if (go_on && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, fuse_mode, store_u))) return rc;
+      if (last && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, ROW_INV_DIAG, 1))) return rc;
+      if (adaptive && go_on) {
+        // the column minimum of the coming step's integrand, for the members whose rule fires (the kernels check again)
+        if (fused) {
+          bool any = false;
+          for (int i = 0; i < B; ++i) any |= fires(i, s);
+          if (any && (rc = chs_launch_colmin_rows_batch(b->stream, b->dMem, B, b->N, b->dtype == CHS_F32))) return rc;
+        } else {
+          for (int i = 0; i < B; ++i)
+            if (fires(i, s) && (rc = chs_launch_mu_colsums(b->m[i], 1))) return rc;
+        }
+      }
       // (the last-step records first: a member whose record the other launch writes moves on to its last step)
       if (last && (rc = launch_tail(b->stream, b->dMem, B, P->col_threads, true, 0))) return rc;
       if (go_on && (rc = launch_tail(b->stream, b->dMem, B, P->col_threads, false, 0))) return rc;
@@ -311,7 +358,7 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     if (nsteps[i] <= 0) continue;
     Engine* E = b->m[i];
     const DevState s = b->hPoll[i];
-    if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && s.rows_written < nsteps[i]) {
+    if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !E->storeU && s.rows_written < nsteps[i]) {
       // the energy rule or the time limit ended this member's call before its last step: its row kernel has been
       // keeping U in registers and hat_U is that of the last completed step -- the field is rebuilt from it (run_steps)
       DevState r = s;

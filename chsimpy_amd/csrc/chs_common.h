@@ -333,6 +333,10 @@ int chs_launch_mu_colsums(Engine* E, int cs_offset);
 int chs_fast_rearm(Engine* E);
 int chs_launch_colmin_rows(Engine* E, int cs_offset, bool decide = false);  // min over the columns of sum(dPartColRows)  // dU -> column-sum minimum of the adaptive-step integrand only
 struct TailArgs;
+struct BatchMember;
+// the batch's column-minimum reduction: the members' partial rows (chs_fast_kernels.h: k_row_inv<ADAPT>) -> partColMin
+int chs_colmin_batch_buffers(Engine* E, BatchMember* r);
+int chs_launch_colmin_rows_batch(hipStream_t s, const BatchMember* mem, int B, int N, bool rows_f32);
 TailArgs chs_tail_args(const Engine* E, int set, int do_pre);  // set < 0: the current partial-sum pointers
 int chs_launch_step_tail(Engine* E, int do_pre);  // fused pipeline: record of step s + time-step control of step s+1
 int chs_launch_pre(Engine* E);                // partials -> state (L2, delt, time)

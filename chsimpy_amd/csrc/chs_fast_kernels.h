@@ -585,19 +585,8 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
 // takes the member's arrays, state and constants in place of the arguments, and leaves at once when the member
 // has no step left in this call (or has halted: the kernels' own check).  The instantiations without it -- the
 // single handle's -- are the same code as before (an empty pack; `if constexpr` drops the batch part).
+// The member record itself (BatchMember) is declared in chs_tail.h, where the batched reduction of chs_pointwise.hip sees it too.
 // ---------------------------------------------------------------------------
-struct BatchMember {
-  DevConsts dc;
-  DevState* st;
-  void* T1;   // the step's T operand: k_col in, fused row kernel out
-  void* T2;   // k_col out, k_row_inv in (aliases T1: the step works in place)
-  void* hat;  // hat_U, updated in place (after a stop: that of the last completed step)
-  void* U;
-  double* partDiag; double* partMu; double* partRa; double* partE2;
-  long long nsteps;  // iterations of the running call: the member's step of a launch is st->rows_written
-  TailArgs tail[3];  // the step tail's inputs: [0] first step (time-step control only), [1] record + control of the
-                     // next step, [2] record of the call's last step
-};
 // (read through the constant address space: the records do not change during a launch, so the compiler may load a
 // field again where it is used instead of keeping it in registers across the kernel)
 typedef const __attribute__((address_space(4))) BatchMember ConstBatchMember;
@@ -627,13 +616,15 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
   using T = typename C::T;
   __shared__ double red[64];
   if constexpr (sizeof...(Batch) != 0) {
-    // batched (FUSE: the members whose call goes on behind this step; !FUSE: those for which it is the last)
-    static_assert(DIAG && !ADAPT, "batches run the fixed-step row kernels");
+    // batched (FUSE: the members whose call goes on behind this step; !FUSE: those for which it is the last; ADAPT: a batch
+    // whose members all adapt their step -- the firing test below is the member's own, on its own step counter)
+    static_assert(DIAG && (FUSE || !ADAPT), "batches run the step's row kernels");
     ConstBatchMember& m = batch_member(mem...);
     const long long done = m.st->rows_written, last = m.nsteps - 1;
     if (FUSE ? done >= last : done != last) return;
     T2 = (const T*)m.T2; U = (T*)m.U; T1 = (T*)m.T1; dc = *(const DevConsts*)&m.dc; st = m.st;
     partDiag = m.partDiag; partMu = m.partMu; partRa = m.partRa;
+    if constexpr (ADAPT) partColRows = (T*)m.partColRows;
   }
   if (st->halt) return;
   T* lds = reinterpret_cast<T*>(chs_dyn_lds);
@@ -1377,7 +1368,10 @@ struct FastPlan {
   // `mem` = the device array of the B member records
   int (*init_batch)() = nullptr;
   int (*col_batch)(Engine* E0, hipStream_t s, const BatchMember* mem, int B, int reverse) = nullptr;
-  int (*row_inv_batch)(Engine* E0, hipStream_t s, const BatchMember* mem, int B, bool fuse) = nullptr;
+  // mode: ROW_INV_DIAG (the members' last step), ROW_INV_FUSED, ROW_INV_FUSED_ADAPT (an adaptive batch: the partial column
+  // sums of the step-size integrand ride along); store_u: the fused kernels write the whole field (a batch whose
+  // step-size sums come from a sweep of U)
+  int (*row_inv_batch)(Engine* E0, hipStream_t s, const BatchMember* mem, int B, int mode, int store_u) = nullptr;
   int col_threads = 0;   // block size of the step's k_col: that of the single handle's riding tail (chs_batch.hip)
 };
 
@@ -1517,6 +1511,9 @@ struct BatchLaunch {
     int rc;
     if ((rc = L::set_lds(k_col<CC, MODE_STEP, const BatchMember*>, L::col_lds))) return rc;
     if ((rc = L::set_lds(k_row_inv<C, true, true, false, const BatchMember*>, L::row_lds))) return rc;
+    if constexpr (L::ADAPT_OK) {
+      if ((rc = L::set_lds(k_row_inv<C, true, true, true, const BatchMember*>, L::row_lds))) return rc;
+    }
     return L::set_lds(k_row_inv<C, true, false, false, const BatchMember*>, L::row_lds);
   }
   static int col(Engine* E0, hipStream_t s, const BatchMember* mem, int B, int reverse) {
@@ -1527,13 +1524,18 @@ struct BatchLaunch {
     CHS_HIP(hipGetLastError());
     return CHS_OK;
   }
-  static int row_inv(Engine* E0, hipStream_t s, const BatchMember* mem, int B, bool fuse) {
+  static int row_inv(Engine* E0, hipStream_t s, const BatchMember* mem, int B, int mode, int store_u) {
     const dim3 grid(C::N / C::C, B);
     const FTables<T> tb = get_tables<T>(E0);
-    if (fuse)
+    if (mode == ROW_INV_FUSED)
       k_row_inv<C, true, true, false, const BatchMember*><<<grid, C::THREADS, L::row_lds, s>>>(
-          nullptr, nullptr, nullptr, tb, E0->dc, nullptr, nullptr, nullptr, nullptr, 0, nullptr, mem);
-    else
+          nullptr, nullptr, nullptr, tb, E0->dc, nullptr, nullptr, nullptr, nullptr, store_u, nullptr, mem);
+    else if (mode == ROW_INV_FUSED_ADAPT) {
+      if constexpr (L::ADAPT_OK)
+        k_row_inv<C, true, true, true, const BatchMember*><<<grid, C::THREADS, L::row_lds, s>>>(
+            nullptr, nullptr, nullptr, tb, E0->dc, nullptr, nullptr, nullptr, nullptr, store_u, nullptr, mem);
+      else { chs_set_error("fused adaptive row kernel is not built for this configuration"); return CHS_EINVAL; }
+    } else
       k_row_inv<C, true, false, false, const BatchMember*><<<grid, C::THREADS, L::row_lds, s>>>(
           nullptr, nullptr, nullptr, tb, E0->dc, nullptr, nullptr, nullptr, nullptr, 1, nullptr, mem);
     CHS_HIP(hipGetLastError());

@@ -557,6 +557,20 @@ __global__ __launch_bounds__(PW_THREADS) void k_colsum_slices(const PT* __restri
     slices[(size_t)blockIdx.y * N + c] = t;
   }
 }
+// (second stage, one block: the column sums of PW_THREADS columns over the slices and their minimum, valid in every thread)
+__device__ __forceinline__ double colmin_block(const double* __restrict__ slices, int N, double* scratch) {
+  const int c = blockIdx.x * PW_THREADS + threadIdx.x;
+  double s = 1.0e300;
+  if (c < N) {
+    double x[CS_SLICES];
+#pragma unroll
+    for (int b = 0; b < CS_SLICES; ++b) x[b] = slices[(size_t)b * N + c];
+    s = 0.0;
+#pragma unroll
+    for (int b = 0; b < CS_SLICES; ++b) s += x[b];
+  }
+  return block_min(s, scratch);
+}
 // `decide` (the fused pipeline with nothing armed that a tail would have to decide: chs_fast_step): the block that finishes
 // last also takes the minimum over the blocks and works out the coming step's coefficients lam1 / lam2 -- the step-size rule of
 // solver.py:184-193 is a function of the current delt and of this minimum alone -- so that the next k_col finds them in the
@@ -569,17 +583,7 @@ __global__ __launch_bounds__(PW_THREADS) void k_colmin_slices(const double* __re
   if (st->halt) return;
   const long long cs = st->computed_steps + cs_offset;
   if (!(adaptive && cs > 500 && (cs % 2) == 0)) return;
-  const int c = blockIdx.x * PW_THREADS + threadIdx.x;
-  double s = 1.0e300;
-  if (c < N) {
-    double x[CS_SLICES];
-#pragma unroll
-    for (int b = 0; b < CS_SLICES; ++b) x[b] = slices[(size_t)b * N + c];
-    s = 0.0;
-#pragma unroll
-    for (int b = 0; b < CS_SLICES; ++b) s += x[b];
-  }
-  const double m = block_min(s, scratch);
+  const double m = colmin_block(slices, N, scratch);
   if (threadIdx.x == 0) {
     partColMin[blockIdx.x] = m;
     if (decide) {
@@ -627,6 +631,88 @@ int chs_launch_colmin_rows(Engine* E, int cs_offset, bool decide) {
   const int rc = launch_colmin(E, E->dPartColRows, E->dtype == CHS_F32, E->nRowBlocks, cs_offset, decide);
   chs_slot_end(E, SLOT_MISC);
   if (rc) return rc;
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The same reduction for a batch whose members adapt their step (chs_batch.hip): two launches cover all members,
+// the member is the grid's last dimension.  A member's partial rows are added as above -- the same slices, the same
+// order inside a block and over the slices -- so its column minimum is bit for bit the single handle's.  Launched
+// behind the row kernels of a step and in front of its tails (the record of the running step has not advanced the
+// counters yet: computed_steps + 1, rows_written = the step's index in the call).  A workgroup leaves at once when
+// its member has halted, has no step behind this one in the call (its row kernel wrote no partial rows) or when the
+// member's rule does not fire on the coming step.  No `decide`: the batch's tail runs in stream order.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool batch_member_fires(const BatchMember& m) {
+  const DevState* st = m.st;
+  if (st->rows_written >= m.nsteps - 1 || st->halt) return false;
+  const long long cs = st->computed_steps + 1;
+  return m.dc.adaptive_time && cs > 500 && (cs % 2) == 0;
+}
+// (the first stage: the body of k_colsum_slices, cached reads -- the batched grids fit the cache -- with the member's
+// arrays; a copy, because k_colsum_slices compiles to other code when it shares the body as a function)
+template <typename PT>
+__global__ __launch_bounds__(PW_THREADS) void k_colsum_slices_batch(const BatchMember* __restrict__ mem, int N) {
+  __shared__ double acc[PW_THREADS];
+  const BatchMember& m = mem[blockIdx.z];
+  if (!batch_member_fires(m)) return;
+  const PT* __restrict__ partRows = (const PT*)m.partColRows;
+  double* __restrict__ slices = m.colSlices;
+  const int nRows = m.nPartRows;
+  const unsigned slice = blockIdx.y;
+  constexpr int NWV = PW_THREADS / 64;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = blockIdx.x * CS_COLS + lane;
+  const int per = (nRows + CS_SLICES - 1) / CS_SLICES;
+  const int r0 = slice * per, r1 = min(r0 + per, nRows);
+  double s = 0.0;
+  if (c < N) {
+    const PT* col = partRows + c;
+    for (int rb = r0 + w; rb < r1; rb += NWV * CS_UN) {
+      PT x[CS_UN];
+#pragma unroll
+      for (int u = 0; u < CS_UN; ++u) {
+        const int r = rb + u * NWV;
+        const PT* src = &col[(size_t)(r < r1 ? r : r0) * N];
+        x[u] = *src;
+      }
+#pragma unroll
+      for (int u = 0; u < CS_UN; ++u) s += (rb + u * NWV < r1) ? (double)x[u] : 0.0;
+    }
+  }
+  acc[threadIdx.x] = s;
+  __syncthreads();
+  if (w == 0 && c < N) {
+    double t = acc[lane];
+#pragma unroll
+    for (int g = 1; g < NWV; ++g) t += acc[g * 64 + lane];
+    slices[(size_t)slice * N + c] = t;
+  }
+}
+__global__ __launch_bounds__(PW_THREADS) void k_colmin_slices_batch(const BatchMember* __restrict__ mem, int N) {
+  __shared__ double scratch[32];
+  const BatchMember& m = mem[blockIdx.y];
+  if (!batch_member_fires(m)) return;
+  const double mn = colmin_block(m.colSlices, N, scratch);
+  if (threadIdx.x == 0 && (int)blockIdx.x < m.nColMin) m.partColMin[blockIdx.x] = mn;
+}
+
+// the per-member buffers of that reduction (a single handle allocates the slices at its first reduction)
+int chs_colmin_batch_buffers(Engine* E, BatchMember* r) {
+  if (!E->dColSlices) CHS_HIP(hipMalloc(&E->dColSlices, sizeof(double) * (size_t)CS_SLICES * E->N));
+  r->partColRows = E->dPartColRows; r->nPartRows = E->nRowBlocks;
+  r->colSlices = E->dColSlices;
+  r->partColMin = E->dPartColMin; r->nColMin = E->nColMinBlocks;
+  E->nColMinCur = E->nColMinBlocks;
+  return CHS_OK;
+}
+
+int chs_launch_colmin_rows_batch(hipStream_t s, const BatchMember* mem, int B, int N, bool rows_f32) {
+  const dim3 g1((N + CS_COLS - 1) / CS_COLS, CS_SLICES, B), g2((N + PW_THREADS - 1) / PW_THREADS, B);
+  if (rows_f32) k_colsum_slices_batch<float><<<g1, PW_THREADS, 0, s>>>(mem, N);
+  else k_colsum_slices_batch<double><<<g1, PW_THREADS, 0, s>>>(mem, N);
+  k_colmin_slices_batch<<<g2, PW_THREADS, 0, s>>>(mem, N);
   CHS_HIP(hipGetLastError());
   return CHS_OK;
 }

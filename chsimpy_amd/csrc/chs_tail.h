@@ -93,6 +93,27 @@ struct TailArgs {
   long long rowsCap = 0;
 };
 
+// One member of a batch (chs_batch.hip) as the batched kernels see it: the step kernels of chs_fast_kernels.h, the
+// batch's tail and the batched column-minimum reduction of chs_pointwise.hip index a device array of these by member.
+struct BatchMember {
+  DevConsts dc;
+  DevState* st;
+  void* T1;   // the step's T operand: k_col in, fused row kernel out
+  void* T2;   // k_col out, k_row_inv in (aliases T1: the step works in place)
+  void* hat;  // hat_U, updated in place (after a stop: that of the last completed step)
+  void* U;
+  double* partDiag; double* partMu; double* partRa; double* partE2;
+  long long nsteps;  // iterations of the running call: the member's step of a launch is st->rows_written
+  TailArgs tail[3];  // the step tail's inputs: [0] first step (time-step control only), [1] record + control of the
+                     // next step, [2] record of the call's last step
+  // adaptive batches (behind everything the fixed-step kernels read: their offsets stay where they were)
+  void* partColRows;   // [nPartRows][N] partial column sums of the step-size integrand, written by the fused row kernel
+                       // in the engine's element type, one row per workgroup
+  double* colSlices;   // [CS_SLICES][N] first stage of their reduction
+  double* partColMin;  // [nColMin] block minima of the column sums: what the tail's step-size rule reads
+  int nPartRows, nColMin;
+};
+
 #define TAIL_NV 8
 #ifndef TAIL_UN
 #define TAIL_UN 8  // independent requests per thread and batch

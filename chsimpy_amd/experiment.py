@@ -220,8 +220,9 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
 
     ``batch`` > 0: the rank's members run ``batch`` at a time as one device workload, every step kernel launched
     once for the whole group (``batch_fn(run_ids, init_params, rand_values, A_list)`` -> their 12-tuples; default
-    run_batch_gpu).  A configuration outside the batch's scope (chsimpy_amd.batch.scope_error) runs member by
-    member instead, with a note."""
+    run_batch_gpu).  An ensemble with ``adaptive_time`` is taken too: its members all adapt their step.  A configuration
+    outside the batch's scope (chsimpy_amd.batch.scope_error: N, engine, jitter) runs member by member instead, with a
+    note."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
@@ -297,6 +298,8 @@ def main(argv=None):
     ap.add_argument('--A-seed', type=int, default=85972)
     ap.add_argument('-K', '--kappa-tilde', type=float, default=None)
     ap.add_argument('--full-sim', action='store_true')
+    ap.add_argument('-a', '--adaptive-time', action='store_true', help='adaptive time stepping (the reference\'s -a)')
+    ap.add_argument('--delt-max', type=float, default=None, help='upper bound of the adaptive step (parameters.py: 9e-8)')
     ap.add_argument('--file-id', default='auto')
     ap.add_argument('--export-csv', default=None)
     ap.add_argument('--Uinit-file', default=None)
@@ -337,6 +340,9 @@ def main(argv=None):
     p = Parameters()
     p.N, p.ntmax, p.full_sim, p.kappa_tilde = a.N, a.ntmax, a.full_sim, a.kappa_tilde
     p.no_gui, p.export_csv, p.Uinit_file = True, a.export_csv, a.Uinit_file
+    p.adaptive_time = a.adaptive_time
+    if a.delt_max is not None:
+        p.delt_max = a.delt_max
     # (CHS_SAME_GPU=1: every rank on device 0 -- rehearsing the multi-rank path with real device work on a one-GPU box)
     p.device = 0 if os.environ.get('CHS_SAME_GPU') == '1' else local_rank
     p.file_id = utils.get_or_create_file_id(a.file_id)

@@ -229,15 +229,16 @@ const char* chs_last_error(void);
 const char* chs_version(void);
 
 /* ---- Batches: B ensemble members advanced together --------------------------------------------------------------
- * A batch holds B members of the same N, dtype and device (the fast engine, N in {128, 256, 512, 1024, 2048}, a fixed
- * time step); every other scalar of chs_consts -- A0, A1, full_sim, time_limit_s, delt, threshold, ... -- is the
- * member's own.  Each step kernel is launched once for all members, so that the short dependent chains of small grids
+ * A batch holds B members of the same N, dtype and device (the fast engine, N in {128, 256, 512, 1024, 2048}) that
+ * either all keep a fixed time step or all adapt it (adaptive_time, solver.py:177-193: each member by its own rule,
+ * counter and delt_max); every other scalar of chs_consts -- A0, A1, full_sim, time_limit_s, delt, delt_max,
+ * threshold, ... -- is the member's own.  Each step kernel is launched once for all members, so that the short dependent chains of small grids
  * overlap each other on the device.  For every member m the semantics are those of chs_prepare / chs_step_n /
  * chs_get_state on a single handle created from consts[m]; every chs_batch_step_n is a literal solve_or_resume call
  * (hat_U = dctn(U) recomputed on entry, solver.py:159; U stored at the end).  One lambda table for all members.
  * chs_batch_create returns CHS_EINVAL (chs_last_error says why) for B < 1, members that differ in N, dtype or device,
- * an N outside the set above, engine = CHS_ENGINE_DIRECT, or adaptive_time != 0 in any member.  Jitter has no
- * batched counterpart.  `member` = -1 addresses every member where noted. */
+ * an N outside the set above, engine = CHS_ENGINE_DIRECT, or a member whose adaptive_time differs from member 0's
+ * (the message names the first such member).  Jitter has no batched counterpart.  `member` = -1 addresses every member where noted. */
 typedef struct chs_batch_s* chs_batch;
 int chs_batch_create(const chs_consts* consts /*[B]*/, int32_t B, const double* lambda, chs_batch* out);
 int chs_batch_destroy(chs_batch b);

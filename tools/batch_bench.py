@@ -6,7 +6,14 @@ Protocol: full_sim, one literal 2000-step call (solve_or_resume(2001) after prep
 (mean and best); members with the A factors of make_rand_values.  Extra rows: 64 x N=2048 (configs[4]'s size) and the
 default experiment (N=512, energy stop, ntmax 1e6, 64 members stopping at different steps).
 
-usage: tools/batch_bench.py [--quick]     (--quick: N=512 fp64 only, B in {1, 16})
+--adaptive: the same members with adaptive_time and delt_max = 4.9e-7/N (the adaptive tests' value: the step grows from
+step 502 on, re-evaluated on every second step), so that three quarters of the 2000 steps run under the step-size rule;
+rows N in {256, 512, 1024} fp64 and N=512 fp32, no default-experiment row.
+
+usage: tools/batch_bench.py [--quick] [--adaptive] [--only N,dtype,B [--once]]
+    --quick: N=512 fp64 only, B in {1, 16}
+    --only:  one batched row and nothing else, e.g. --only 512,float64,16; --once: a single call without warm-up or
+             repetitions (what a kernel trace should hold)
 """
 import os
 import sys
@@ -24,12 +31,15 @@ from chsimpy_amd.batch import BatchSolver  # noqa: E402
 KAPPA = 0.0002989112919661156
 STEPS = 2000
 REPS = 3
+ADAPTIVE = False
 
 
 def members(N, B, dtype='float64', ntmax=STEPS + 1, full_sim=True):
     init = chsimpy_amd.Parameters()
     init.N, init.ntmax, init.full_sim, init.kappa_tilde, init.dtype = N, ntmax, full_sim, KAPPA, dtype
     init.file_id = '/tmp/batch_bench'
+    if ADAPTIVE:
+        init.adaptive_time, init.delt_max = True, 4.9e-7 / N
     ep = ex.ExperimentParams()
     ep.runs = B
     rv, al, _ = ex.make_rand_values(ep)
@@ -37,6 +47,9 @@ def members(N, B, dtype='float64', ntmax=STEPS + 1, full_sim=True):
 
 
 def timed(fn, reps=REPS):
+    if '--once' in sys.argv:
+        t = fn()
+        return t, t
     fn()                                  # warm-up
     ts = []
     for _ in range(reps):
@@ -70,6 +83,8 @@ def batched(N, B, dtype):
         return time.perf_counter() - t0
     mean, best = timed(run)
     assert all(s.solution.computed_steps == STEPS + 1 for s in bs.solvers)
+    if ADAPTIVE:   # the step did adapt, every member's
+        assert all(len(set(s.solution.timedata.data()[:, 8])) > 100 for s in bs.solvers)
     bs.close(fetch_U=False)
     return B * STEPS / mean, B * STEPS / best
 
@@ -103,11 +118,20 @@ def default_experiment(B=64, batch=16):
 
 
 def main():
+    global ADAPTIVE
     quick = '--quick' in sys.argv
+    ADAPTIVE = '--adaptive' in sys.argv
+    mode = 'adaptive step (delt_max = 4.9e-7/N), ' if ADAPTIVE else ''
+    if '--only' in sys.argv:
+        N, dt, B = sys.argv[sys.argv.index('--only') + 1].split(',')
+        b_mean, b_best = batched(int(N), int(B), dt)
+        print(f"N={N} {dt} {mode}batch B={int(B):3d}: {b_mean:9.0f} ({b_best:9.0f}) member-steps/s", flush=True)
+        return
     rows = ([(512, 'float64')] if quick else
-            [(256, 'float64'), (512, 'float64'), (1024, 'float64'), (2048, 'float64'), (512, 'float32')])
+            [(256, 'float64'), (512, 'float64'), (1024, 'float64')] + ([] if ADAPTIVE else [(2048, 'float64')])
+            + [(512, 'float32')])
     Bs = (1, 16) if quick else (1, 4, 16, 64)
-    print(f"# batch bench: full_sim, one literal {STEPS}-step call, 1 warm-up + {REPS} reps; member-steps/s mean (best)")
+    print(f"# batch bench: full_sim, {mode}one literal {STEPS}-step call, 1 warm-up + {REPS} reps; member-steps/s mean (best)")
     for N, dt in rows:
         s_mean, s_best = single(N, dt)
         print(f"N={N} {dt} single handle: {s_mean:9.0f} ({s_best:9.0f}) steps/s", flush=True)
@@ -118,7 +142,7 @@ def main():
             b_mean, b_best = batched(N, B, dt)
             print(f"N={N} {dt} batch B={B:3d}: {b_mean:9.0f} ({b_best:9.0f}) member-steps/s   "
                   f"x{b_mean / s_mean:5.2f} single, x{b_mean / c_mean:5.2f} concurrent=3", flush=True)
-    if not quick:
+    if not quick and not ADAPTIVE:
         r = default_experiment()
         for label, (dt, steps, stops) in r.items():
             print(f"default experiment N=512 energy stop, 64 members, {label}: {dt:7.2f} s, {steps} member-steps "
