@@ -34,6 +34,7 @@ SYMBOLS = (
     'chs_last_error', 'chs_version',
     'chs_batch_create', 'chs_batch_destroy', 'chs_batch_set_U', 'chs_batch_init_U_pcg64', 'chs_batch_get_U',
     'chs_batch_prepare', 'chs_batch_step_n', 'chs_batch_get_state', 'chs_batch_set_state',
+    'chs_batch_step_n_queued', 'chs_batch_member_rows',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create)
@@ -143,6 +144,8 @@ def load():
     lib.chs_batch_step_n.argtypes = [vp, i64p, C.c_int32, dp, i64p, C.POINTER(C.c_int32)]
     lib.chs_batch_get_state.argtypes = [vp, C.c_int32, C.POINTER(chs_state)]
     lib.chs_batch_set_state.argtypes = [vp, C.c_int32, C.POINTER(chs_state)]
+    lib.chs_batch_step_n_queued.argtypes = [vp, C.c_int32, i64p, C.c_int32, i64p, C.POINTER(C.c_int32)]
+    lib.chs_batch_member_rows.argtypes = [vp, C.c_int32, dp, C.c_int64]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -376,6 +379,26 @@ class Batch:
         if rc not in (CHS_OK, CHS_ENAN):
             self._check(rc, 'chs_batch_step_n')
         return [rows[m, :done[m]].copy() for m in range(self.B)], [int(x) for x in status]
+
+    def step_n_queued(self, nsteps, seats):
+        """`step_n` with the members taking turns in `seats` seats on the device (chs_batch_step_n_queued): the same
+        return value, bit for bit."""
+        n = np.ascontiguousarray([max(int(k), 0) for k in nsteps], dtype=np.int64)
+        if n.size != self.B:
+            raise ValueError(f"nsteps needs {self.B} entries, got {n.size}")
+        done = np.zeros(self.B, dtype=np.int64)
+        status = np.zeros(self.B, dtype=np.int32)
+        rc = self.lib.chs_batch_step_n_queued(self._h, int(seats), n.ctypes.data_as(C.POINTER(C.c_int64)), 0,
+                                              done.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc not in (CHS_OK, CHS_ENAN):
+            self._check(rc, 'chs_batch_step_n_queued')
+        rows = []
+        for m in range(self.B):
+            r = np.empty((int(done[m]), 9), dtype=np.float64)
+            self._check(self.lib.chs_batch_member_rows(self._h, m, _dptr(r), int(done[m])), 'chs_batch_member_rows')
+            rows.append(r)
+        return rows, [int(x) for x in status]
 
     def get_state(self, member):
         s = chs_state()

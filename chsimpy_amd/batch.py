@@ -15,6 +15,12 @@ step counter and ``delt_max``); anything else raises ``ValueError`` before the d
     bs.prepare()
     solutions = bs.solve_or_resume()      # one Solution per member
     bs.close()
+
+``BatchSolver(params_list, seats=S)`` runs the members as a seat queue: S seats are launched every step, and when a
+member stops or has done its call the next one in member order takes its seat on the device
+(``chs_batch_step_n_queued``).  A default ensemble's members stop at their own steps, so a plain batch thins out
+towards the end of every call; a queue of all the runs keeps S of them going.  The results are bit for bit the plain
+batch's.
 """
 import numpy as np
 
@@ -40,10 +46,13 @@ def _key(params):
     return (int(params.N), _lib.DTYPES[str(getattr(params, 'dtype', 'float64'))], int(getattr(params, 'device', 0) or 0))
 
 
-def validate(params_list):
-    """Raise ValueError unless the members can share one batch (host-side checks only)."""
+def validate(params_list, seats=None):
+    """Raise ValueError unless the members can share one batch (host-side checks only).  ``seats``: the seats of a
+    queue (None: a plain batch)."""
     if len(params_list) < 1:
         raise ValueError("a batch needs at least one member")
+    if seats is not None and (isinstance(seats, bool) or int(seats) != seats or int(seats) < 1):
+        raise ValueError(f"seats={seats!r}: a queue needs seats >= 1")
     for i, p in enumerate(params_list):
         why = scope_error(p)
         if why:
@@ -82,9 +91,10 @@ class _Member:
 
 
 class BatchSolver:
-    def __init__(self, params_list, U_init=None):
+    def __init__(self, params_list, U_init=None, seats=None):
         params_list = list(params_list)
-        validate(params_list)
+        validate(params_list, seats)
+        self.seats = None if seats is None else int(seats)
         B = len(params_list)
         if U_init is None or (isinstance(U_init, np.ndarray) and U_init.ndim == 2):
             inits = [U_init] * B
@@ -174,7 +184,7 @@ class BatchSolver:
                 sol.__dict__['_U_print'] = None
             itbegin = 1 if sol.computed_steps == 1 else 0
             counts.append(max(int(n) - itbegin, 0))
-        rows, status = b.step_n(counts)
+        rows, status = b.step_n(counts) if self.seats is None else b.step_n_queued(counts, self.seats)
         self.member_errors = {}
         for m, s in enumerate(self.solvers):
             try:

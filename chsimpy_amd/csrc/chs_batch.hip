@@ -20,6 +20,12 @@
 // the device from its own step counter; the host follows the counters (Engine::csHost) only to leave the reduction
 // out on steps where it knows that no running member fires.  A configuration without the fused adaptive row kernel
 // (N = 128: eight rows per workgroup) takes the sums from a sweep of U as its single handle does, member by member.
+//
+// The seat queue (chs_batch_step_n_queued): the same step kernels launched over a device array of `seats` records
+// instead of over all members.  The batch's own array holds the records of the members in waiting; behind the tails
+// k_seat_batch hands the seat of a member that has stopped or done its steps to the next one in member order, on the
+// device.  The host never learns who sits where: it issues every step's kernels for every seat and follows the members
+// through its polls of their states alone.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -52,6 +58,57 @@ static int launch_tail(hipStream_t s, const BatchMember* mem, int B, int col_thr
   return CHS_OK;
 }
 
+// The seat change of the queue.  `seat[seats]` are the records the step kernels of the coming launches index, `wait[R]`
+// the records of all members of the call in member order, q[0] the number of the first member that has not been
+// looked at yet and q[1 + m] the global step in front of which member m was seated (-1: not so far).  ONE wavefront
+// walks the seats in ascending order, so who gets which seat is a function of the members' stop steps alone: a seat
+// is free when its member has halted or has written the last record of its call (a vacant seat's record has
+// nsteps = 0); it goes to the next waiting member that has steps to do and has not halted already (a time limit
+// below the first step: its `pre_only` tail stopped it).  Lanes look at 64 seats / 64 waiting members at a time, the
+// record is copied by all lanes in 8-byte words: plain vector loads and stores, nothing here is written by the
+// scalar unit.  The step kernels read the records through the constant address space (scalar loads, batch_member):
+// they see the new record because they are later launches of the same stream and a kernel's start invalidates the
+// scalar cache -- what the hipMemcpyAsync of the records at the start of every call relies on already.
+// Launched only in front of EVEN global steps (the host's choice, `step`): k_col walks its tiles in the direction the
+// launch's step parity gives it, the partial sums of E2 land in block order and the tail adds them in that order -- a
+// member seated in front of an odd step would get E2 of every step in the other summation order than the unqueued
+// batch, where all members start at step 0.  A freed seat so idles one step at the most.
+static_assert(sizeof(BatchMember) % 8 == 0 && alignof(BatchMember) == 8, "the seat kernel copies records in 8-byte words");
+__global__ __launch_bounds__(64) void k_seat_batch(BatchMember* seat, int seats, const BatchMember* __restrict__ wait, int R,
+                                                   long long* q, long long step) {
+  const int lane = threadIdx.x;
+  const long long head0 = q[0];
+  long long head = head0;
+  for (int s0 = 0; s0 < seats && head < R; s0 += 64) {
+    const int j = s0 + lane;
+    bool vacant = false;
+    if (j < seats) {
+      const DevState* st = seat[j].st;
+      vacant = st->halt || st->rows_written >= seat[j].nsteps;
+    }
+    unsigned long long free_seats = __ballot(vacant);
+    while (free_seats && head < R) {
+      const int js = s0 + __ffsll(free_seats) - 1;
+      int next = -1;
+      while (head < R) {
+        const long long c = head + lane;
+        bool runs = false;
+        if (c < R) runs = wait[c].nsteps > 0 && !wait[c].st->halt;
+        const unsigned long long found = __ballot(runs);
+        if (found) { next = (int)head + __ffsll(found) - 1; head = next + 1; break; }
+        head += 64;
+      }
+      if (next < 0) break;
+      free_seats &= free_seats - 1;
+      const unsigned long long* src = reinterpret_cast<const unsigned long long*>(wait + next);
+      unsigned long long* dst = reinterpret_cast<unsigned long long*>(seat + js);
+      for (int w = lane; w < (int)(sizeof(BatchMember) / 8); w += 64) dst[w] = src[w];
+      if (lane == 0) q[1 + next] = step;
+    }
+  }
+  if (lane == 0 && head != head0) q[0] = head < R ? head : R;
+}
+
 namespace {
 struct Batch {
   int B = 0, N = 0, dtype = CHS_F64, device = 0;
@@ -62,6 +119,14 @@ struct Batch {
   std::vector<BatchMember> hMem;
   DevState* hPoll = nullptr;     // pinned [5][B]: slot 0 = the end of a call, 1..4 = the polls behind the step batches
   hipEvent_t evPoll[4] = {nullptr, nullptr, nullptr, nullptr};
+  // the seat queue (chs_batch_step_n_queued; allocated at its first call)
+  BatchMember* dSeat = nullptr;  // [seatCap] the records the step kernels index; dMem holds the waiting members' then
+  int seatCap = 0;
+  long long* dQueue = nullptr;   // [1 + B]: head of the queue, the members' seating steps (k_seat_batch)
+  long long* hQueue = nullptr;   // pinned [5][1 + B], slots as in hPoll
+  std::vector<BatchMember> hSeat;
+  std::vector<long long> hQueue0;
+  std::vector<std::vector<double>> qRows;  // the members' rows of the last queued call (chs_batch_member_rows)
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -78,6 +143,9 @@ void batch_free(Batch* b) {
     chs_destroy((chs_handle)b->m[i]);
   }
   if (b->dMem) hipFree(b->dMem);
+  if (b->dSeat) hipFree(b->dSeat);
+  if (b->dQueue) hipFree(b->dQueue);
+  if (b->hQueue) hipHostFree(b->hQueue);
   if (b->hPoll) hipHostFree(b->hPoll);
   for (auto e : b->evPoll) if (e) hipEventDestroy(e);
   if (b->stream) hipStreamDestroy(b->stream);
@@ -382,5 +450,273 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     chs_set_error("NaN in a recorded scalar (timedata.py:10) of a member: U left (0,1)");
     return CHS_ENAN;
   }
+  return CHS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The seat queue: chs_batch_step_n over `seats` records that the members of the batch take turns in.
+// ---------------------------------------------------------------------------
+static int queue_buffers(Batch* b, int seats) {
+  const size_t nq = 1 + (size_t)b->B;
+  if (!b->dQueue) CHS_HIP(hipMalloc(&b->dQueue, sizeof(long long) * nq));
+  if (!b->hQueue) CHS_HIP(hipHostMalloc((void**)&b->hQueue, sizeof(long long) * 5 * nq, hipHostMallocDefault));
+  if (seats > b->seatCap) {
+    if (b->dSeat) { CHS_HIP(hipStreamSynchronize(b->stream)); CHS_HIP(hipFree(b->dSeat)); b->dSeat = nullptr; b->seatCap = 0; }
+    CHS_HIP(hipMalloc(&b->dSeat, sizeof(BatchMember) * (size_t)seats));
+    b->seatCap = seats;
+  }
+  return CHS_OK;
+}
+
+// The global step count of the call when no member stops early: the members take the seats in member order, a seat
+// changes hands in front of an even step (k_seat_batch).  A member that stops early only lets the ones behind it start
+// sooner, so this bounds the steps to issue; with as many seats as members it is the largest nsteps.
+static int64_t queue_step_bound(const int64_t* nsteps, int R, int seats) {
+  std::vector<int64_t> free_at((size_t)seats, 0);
+  int64_t bound = 0;
+  for (int i = 0; i < R; ++i) {
+    if (nsteps[i] <= 0) continue;
+    size_t k = 0;
+    for (size_t j = 1; j < free_at.size(); ++j) if (free_at[j] < free_at[k]) k = j;
+    const int64_t start = free_at[k] + (free_at[k] & 1);
+    free_at[k] = start + nsteps[i];
+    if (free_at[k] > bound) bound = free_at[k];
+  }
+  return bound;
+}
+
+// chs_batch_step_n with the members taking turns in `seats` seats: the entry of every member up front (the single
+// handle's code, as in chs_batch_step_n), then every step kernel launched over the seats; k_seat_batch hands a seat
+// on.  The host does not know who sits where, so it leaves nothing out that a seated member might need: the fused row
+// kernel, the normal tail and (adaptive) the reduction go out on every step, the last-step pair from the first step on
+// at which the call of some unfinished member may end.  The kernels decide per member, as they always did.
+extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t* nsteps, int32_t flags,
+                                       int64_t* steps_done, int32_t* status) {
+  Batch* b = as_batch(h);
+  if (!b || !nsteps || !steps_done || !status) return bad("chs_batch_step_n_queued: null argument");
+  if (flags != 0) return bad("chs_batch_step_n_queued: flags is reserved and must be 0");
+  if (seats < 1) return bad("chs_batch_step_n_queued: seats must be >= 1");
+  const int R = b->B;
+  const int S = seats < R ? seats : R;
+  int running = 0;
+  for (int i = 0; i < R; ++i) {
+    if (nsteps[i] > 0 && !b->m[i]->prepared) {
+      chs_set_error("chs_batch_step_n_queued: member " + std::to_string(i) + " not prepared (solver.py:139)");
+      return CHS_ESTATE;
+    }
+    running += nsteps[i] > 0;
+  }
+  CHS_HIP(hipSetDevice(b->device));
+  int rc;
+  if ((rc = queue_buffers(b, S))) return rc;
+  int batch_steps = 1024;
+  bool adaptive = false, fused = true;
+  for (int i = 0; i < R; ++i) {
+    const Engine* E = b->m[i];
+    adaptive |= E->dc.adaptive_time != 0;
+    fused &= E->fusedAdapt && E->dPartColRows != nullptr;
+  }
+  fused &= adaptive;
+  b->qRows.assign((size_t)R, std::vector<double>());
+  // entry of every member that runs, exactly as in chs_batch_step_n: the records are those of the waiting members
+  for (int i = 0; i < R; ++i) {
+    Engine* E = b->m[i];
+    BatchMember& r = b->hMem[(size_t)i];
+    std::memset((void*)&r, 0, sizeof r);
+    const int64_t n = nsteps[i] > 0 ? nsteps[i] : 0;
+    r.nsteps = n;
+    steps_done[i] = 0;
+    status[i] = CHS_OK;
+    r.st = E->dState;
+    if (n == 0) continue;   // sits the call out: never seated, state and field stay as they are
+    E->stateCached = false; E->resident = false; E->keepResident = false;
+    E->tailDeferred = false; E->tailGated = false; E->preRider = false;
+    E->storeU = adaptive && !fused;
+    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) batch_steps = E->batchSteps < batch_steps ? E->batchSteps : batch_steps;
+    if ((rc = chs_launch_call_begin(E))) return rc;
+    if ((rc = chs_fast_enter_fused(E))) return rc;
+    E->hat_valid = true;
+    r.dc = E->dc;
+    r.T1 = E->dT1;
+    r.T2 = E->dT1;
+    r.hat = E->dHat;
+    r.U = E->dU;
+    r.partDiag = E->dPartDiag; r.partMu = E->dPartMu; r.partRa = E->dPartRa; r.partE2 = E->dPartE2;
+    r.tail[0] = chs_tail_args(E, -1, 1);
+    r.tail[0].pre_only = 1;
+    r.tail[1] = chs_tail_args(E, -1, 1);
+    r.tail[2] = chs_tail_args(E, -1, 0);
+    if (adaptive) {
+      if (fused && (rc = chs_colmin_batch_buffers(E, &r))) return rc;
+      if ((rc = chs_launch_mu_colsums(E, 0))) return rc;
+      if ((rc = chs_launch_pre(E))) return rc;
+    }
+  }
+  if (const char* bs = getenv("CHS_BATCH_STEPS")) {
+    const long v = atol(bs);
+    if (v >= 1 && v <= 8192) batch_steps = (int)v;
+  }
+  // every seat vacant (no step in the call, somebody's state to look at); the queue at member 0, nobody seated
+  b->hSeat.assign((size_t)S, BatchMember());
+  for (BatchMember& v : b->hSeat) { std::memset((void*)&v, 0, sizeof v); v.st = b->m[0]->dState; }
+  b->hQueue0.assign(1 + (size_t)R, -1);
+  b->hQueue0[0] = 0;
+  const size_t nq = 1 + (size_t)R;
+  CHS_HIP(hipMemcpyAsync(b->dMem, b->hMem.data(), sizeof(BatchMember) * (size_t)R, hipMemcpyHostToDevice, b->stream));
+  CHS_HIP(hipMemcpyAsync(b->dSeat, b->hSeat.data(), sizeof(BatchMember) * (size_t)S, hipMemcpyHostToDevice, b->stream));
+  CHS_HIP(hipMemcpyAsync(b->dQueue, b->hQueue0.data(), sizeof(long long) * nq, hipMemcpyHostToDevice, b->stream));
+  Engine* E0 = b->m[0];
+  FastPlan* P = (FastPlan*)E0->dTw;
+  // the first step's time-step control of ALL members, once: over the seats it would also run for members in mid-run
+  if (running > 0 && !adaptive) {
+    if ((rc = launch_tail(b->stream, b->dMem, R, P->col_threads, false, 1))) return rc;
+  }
+  const int64_t bound = queue_step_bound(nsteps, R, S);
+  if (running > 0) {
+    k_seat_batch<<<1, 64, 0, b->stream>>>(b->dSeat, S, b->dMem, R, b->dQueue, 0);
+    CHS_HIP(hipGetLastError());
+  }
+  const int fuse_mode = fused ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED;
+  const int store_u = (adaptive && !fused) ? 1 : 0;
+  std::vector<int64_t> copied((size_t)R, 0);
+  // The last-step pair of member i belongs to step seated + nsteps[i] - 1 exactly: without it the member would stand at
+  // its last step while k_col goes on updating its hat_U.  While the seating step is not known, seated[i] is a lower
+  // bound of it (0, then what the polls show) and the pair goes out on EVERY step from seated[i] + nsteps[i] - 1 on;
+  // once a poll has shown the step (`known`), on that one step.  The first `seats` members that run are seated in front
+  // of step 0.
+  std::vector<int64_t> seated((size_t)R, 0);
+  std::vector<char> known((size_t)R, 0), served((size_t)R, 0);
+  std::vector<char> finished((size_t)R, 0);       // (as far as the polls have shown)
+  for (int i = 0, k = 0; i < R; ++i) {
+    finished[(size_t)i] = nsteps[i] <= 0;
+    if (nsteps[i] > 0 && k++ < S) known[(size_t)i] = 1;
+  }
+  bool all_seated = running <= S;                 // nobody waits (any more): no seat changes hands
+  // rows [copied, w) of member i out of its ring into its host array
+  auto take_rows = [&](int i, int64_t w) {
+    if (w <= copied[(size_t)i]) return (int)CHS_OK;
+    std::vector<double>& v = b->qRows[(size_t)i];
+    v.resize((size_t)w * 9);
+    const int r = copy_member_rows(b->m[i], v.data(), copied[(size_t)i], w);
+    copied[(size_t)i] = w;
+    return r;
+  };
+  int64_t issued = 0;
+  int64_t poll_issued[4] = {0, 0, 0, 0};
+  int poll = 0;
+  bool stopped = false;
+  while (issued < bound && !stopped) {
+    int64_t nb = bound - issued;
+    if (nb > batch_steps) nb = batch_steps;
+    for (int64_t s = issued; s < issued + nb; ++s) {
+      // may the call of an unfinished member end with this step?
+      bool last = false;
+      for (int i = 0; i < R; ++i) {
+        if (finished[(size_t)i] || served[(size_t)i] || s < seated[(size_t)i] + nsteps[i] - 1) continue;
+        last = true;
+        served[(size_t)i] = known[(size_t)i];
+      }
+      if ((rc = P->col_batch(E0, b->stream, b->dSeat, S, (s & 1) ? 1 : 0))) return rc;
+      if ((rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, fuse_mode, store_u))) return rc;
+      if (last && (rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, ROW_INV_DIAG, 1))) return rc;
+      if (adaptive) {
+        if (fused) {
+          if ((rc = chs_launch_colmin_rows_batch(b->stream, b->dSeat, S, b->N, b->dtype == CHS_F32))) return rc;
+        } else {
+          // (the sweep of U works on the member's own arrays, seated or not: what it leaves for a member in waiting is
+          // written again behind that member's own row kernel before its tail reads it)
+          for (int i = 0; i < R; ++i)
+            if (!finished[(size_t)i] && (rc = chs_launch_mu_colsums(b->m[i], 1))) return rc;
+        }
+      }
+      // (the last-step records first, as in chs_batch_step_n)
+      if (last && (rc = launch_tail(b->stream, b->dSeat, S, P->col_threads, true, 0))) return rc;
+      if ((rc = launch_tail(b->stream, b->dSeat, S, P->col_threads, false, 0))) return rc;
+      if (!all_seated && ((s + 1) & 1) == 0 && s + 1 < bound) {
+        k_seat_batch<<<1, 64, 0, b->stream>>>(b->dSeat, S, b->dMem, R, b->dQueue, (long long)(s + 1));
+        CHS_HIP(hipGetLastError());
+      }
+    }
+    issued += nb;
+    if (issued < bound) {
+      const int slot = 1 + (poll & 3);
+      for (int i = 0; i < R; ++i)
+        if (!finished[(size_t)i])
+          CHS_HIP(hipMemcpyAsync(&b->hPoll[(size_t)slot * R + i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
+      CHS_HIP(hipMemcpyAsync(b->hQueue + (size_t)slot * nq, b->dQueue, sizeof(long long) * nq, hipMemcpyDeviceToHost, b->stream));
+      CHS_HIP(hipEventRecord(b->evPoll[poll & 3], b->stream));
+      poll_issued[poll & 3] = issued;
+      if (poll >= 1) {
+        const int prev = (poll - 1) & 3;
+        CHS_HIP(hipEventSynchronize(b->evPoll[prev]));
+        const DevState* ps = &b->hPoll[(size_t)(1 + prev) * R];
+        const long long* pq = b->hQueue + (size_t)(1 + prev) * nq;
+        bool all = true;
+        for (int i = 0; i < R; ++i) {
+          if (finished[(size_t)i]) continue;   // (its slot was not fetched; its rows were taken when it was found finished)
+          const int64_t w = ps[i].rows_written < nsteps[i] ? ps[i].rows_written : nsteps[i];
+          if ((rc = take_rows(i, w))) return rc;
+          if (ps[i].halt || ps[i].rows_written >= nsteps[i]) finished[(size_t)i] = 1;
+          else all = false;
+          // seated by then: the step is known; still waiting: not before the steps that had been issued
+          if (pq[1 + i] >= 0) { seated[(size_t)i] = (int64_t)pq[1 + i]; known[(size_t)i] = 1; }
+          else if (!known[(size_t)i]) seated[(size_t)i] = poll_issued[prev];
+        }
+        if (pq[0] >= R) all_seated = true;
+        if (all) stopped = true;
+      }
+      ++poll;
+    }
+  }
+  for (int i = 0; i < R; ++i)
+    if (nsteps[i] > 0)
+      CHS_HIP(hipMemcpyAsync(&b->hPoll[i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
+  CHS_HIP(hipStreamSynchronize(b->stream));
+  bool any_nan = false;
+  for (int i = 0; i < R; ++i) {
+    if (nsteps[i] <= 0) continue;
+    Engine* E = b->m[i];
+    const DevState s = b->hPoll[i];
+    if (!s.halt && s.rows_written < nsteps[i]) {
+      chs_set_error("chs_batch_step_n_queued: member " + std::to_string(i) + " was left with steps to do");
+      return CHS_ESTATE;
+    }
+    if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !E->storeU && s.rows_written < nsteps[i]) {
+      // stopped before its last step: the field is rebuilt from hat_U of the last completed step (chs_batch_step_n) --
+      // the member's own arrays, whoever has its seat by now
+      DevState r = s;
+      r.halt = 0;
+      CHS_HIP(hipMemcpy(E->dState, &r, sizeof r, hipMemcpyHostToDevice));
+      if ((rc = chs_fast_recover_u(E))) return rc;
+      CHS_HIP(hipStreamSynchronize(b->stream));
+      CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
+    }
+    if (s.halt) E->hat_valid = false;
+    E->csHost = s.computed_steps;
+    const int64_t done = s.rows_written < nsteps[i] ? s.rows_written : nsteps[i];
+    steps_done[i] = done;
+    if ((rc = take_rows(i, done))) return rc;
+    std::vector<double>& mr = b->qRows[(size_t)i];
+    // solver.py:230 `domtime = self.time_passed ** (1 / 3)` with the host libm
+    for (int64_t k = 0; k < done; ++k) mr[(size_t)k * 9 + 4] = pow(mr[(size_t)k * 9 + 4], 1.0 / 3.0);
+    if (s.nan_flag) { status[i] = CHS_ENAN; any_nan = true; }
+  }
+  if (any_nan) {
+    chs_set_error("NaN in a recorded scalar (timedata.py:10) of a member: U left (0,1)");
+    return CHS_ENAN;
+  }
+  return CHS_OK;
+}
+
+// rows of member `member` from the last chs_batch_step_n_queued: n = its steps_done
+extern "C" int chs_batch_member_rows(chs_batch h, int32_t member, double* rows, int64_t n) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_member_rows: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_member_rows: no such member");
+  const std::vector<double>* v = (size_t)member < b->qRows.size() ? &b->qRows[(size_t)member] : nullptr;
+  const int64_t have = v ? (int64_t)(v->size() / 9) : 0;
+  if (n < 0 || n > have) return bad("chs_batch_member_rows: member " + std::to_string(member) + " has " + std::to_string(have) + " rows");
+  if (n > 0 && !rows) return bad("chs_batch_member_rows: rows is null");
+  if (n > 0) std::memcpy(rows, v->data(), sizeof(double) * 9 * (size_t)n);
   return CHS_OK;
 }

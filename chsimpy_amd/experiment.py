@@ -138,13 +138,14 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
     return rec
 
 
-def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True):
+def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
-    run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple."""
+    run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
+    members run as a seat queue, that many at a time (None: all of them from the first step on)."""
     from .batch import BatchSolver
     from .simulator import Simulator
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
-    bs = BatchSolver([r[0] for r in runs], U_init)
+    bs = BatchSolver([r[0] for r in runs], U_init, seats=seats)
     try:
         bs.prepare()
         solutions = bs.solve_or_resume()
@@ -210,7 +211,7 @@ def write_results(file_id, records):
 
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
-                 concurrent=1, batch=0, batch_fn=None):
+                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -222,7 +223,12 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
     once for the whole group (``batch_fn(run_ids, init_params, rand_values, A_list)`` -> their 12-tuples; default
     run_batch_gpu).  An ensemble with ``adaptive_time`` is taken too: its members all adapt their step.  A configuration
     outside the batch's scope (chsimpy_amd.batch.scope_error: N, engine, jitter) runs member by member instead, with a
-    note."""
+    note.
+
+    ``queue`` (with ``batch`` > 0): the rank's members form one seat queue with ``batch`` seats instead of groups of
+    ``batch`` -- a member that stops hands its seat to the next one on the device, so the device does not run the tail
+    of every group nearly empty.  Every member of a queue owns its device arrays from the start, so the runs are cut
+    into queues of at most ``queue_members``; ``batch_fn`` is called once per queue."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
@@ -236,11 +242,14 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
             batch = 0
         else:
             def batch_fn(run_ids, p, rv, al):
+                if queue:
+                    return run_batch_gpu(run_ids, p, rv, al, U_init, seats=batch)
                 return run_batch_gpu(run_ids, p, rv, al, U_init)
     if batch > 0:
         local = []
-        for k in range(0, len(ids), batch):
-            local.extend(batch_fn(ids[k:k + batch], init_params, rand_values, A_list))
+        group = max(int(queue_members), 1) if queue else batch
+        for k in range(0, len(ids), group):
+            local.extend(batch_fn(ids[k:k + group], init_params, rand_values, A_list))
     elif concurrent > 1 and len(ids) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=concurrent) as pool:
@@ -306,6 +315,10 @@ def main(argv=None):
     ap.add_argument('--concurrent', type=int, default=2, help='ensemble members running at once per GPU')
     ap.add_argument('--batch', type=int, default=0, help='advance a rank\'s members this many at a time as one device '
                     'workload (0: one member per engine handle, see --concurrent)')
+    ap.add_argument('--queue', action='store_true', help='with --batch B: the rank\'s members form one seat queue of B seats; '
+                    'a member that stops hands its seat to the next one on the device')
+    ap.add_argument('--queue-members', type=int, default=256, help='members of one queue at the most (each owns its device '
+                    'arrays from the start)')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
     ap.add_argument('--backend', default=os.environ.get('CHS_DIST_BACKEND', 'nccl'),
@@ -354,10 +367,12 @@ def main(argv=None):
         write_metadata(p.file_id, ep, extra=[f"ranks, {world}", f"concurrent_per_rank, {a.concurrent}",
                                              f"host_cores_per_rank, {'all' if pinned is None else len(pinned)}"]
                        + ([f"batch_per_rank, {a.batch}"] if a.batch > 0 else [])
+                       + ([f"queue_members, {a.queue_members}"] if (a.batch > 0 and a.queue) else [])
                        + (["dry_run, True"] if a.dry_run else []))
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
-                           batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None)
+                           batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
+                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)

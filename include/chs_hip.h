@@ -258,6 +258,19 @@ int chs_batch_step_n(chs_batch b, const int64_t* nsteps /*[B]*/, int32_t flags,
                      double* rows /*[B][max nsteps][9]*/, int64_t* steps_done /*[B]*/, int32_t* status /*[B]*/);
 int chs_batch_get_state(chs_batch b, int32_t member, chs_state* out);
 int chs_batch_set_state(chs_batch b, int32_t member, const chs_state* in);
+/* The seat queue: chs_batch_step_n with the members taking turns on the device.  Every step kernel is launched over
+ * `seats` seats; when the member in a seat stops (energy rule, time limit, NaN) or has done its nsteps, the next
+ * member that waits takes the seat on the device, without a host round trip -- members take seats in member order, a
+ * seat changes hands in front of an even step of the call (so that every member walks its column tiles in the order it
+ * would in chs_batch_step_n).  Member by member the call means what chs_batch_step_n means, and its results are bit
+ * for bit those of chs_batch_step_n: a literal solve_or_resume call, the same stop rules, NaN handling and rebuild of U
+ * after a stop; nsteps[m] = 0 sits the call out.  A batch of R members is a queue of R members: seats >= R behaves
+ * like chs_batch_step_n; seats < 1 and flags != 0 return CHS_EINVAL.  The rows are kept by the batch as the polls of
+ * the call copy them out of the members' rings (no [R][max nsteps][9] array: 72 MB per member at ntmax = 1e6) until
+ * the next queued call; chs_batch_member_rows hands over the first n <= steps_done[member] of them. */
+int chs_batch_step_n_queued(chs_batch b, int32_t seats, const int64_t* nsteps /*[R]*/, int32_t flags,
+                            int64_t* steps_done /*[R]*/, int32_t* status /*[R]*/);
+int chs_batch_member_rows(chs_batch b, int32_t member, double* rows /*[n][9]*/, int64_t n);
 
 #ifdef __cplusplus
 }

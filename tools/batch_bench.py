@@ -10,7 +10,13 @@ default experiment (N=512, energy stop, ntmax 1e6, 64 members stopping at differ
 step 502 on, re-evaluated on every second step), so that three quarters of the 2000 steps run under the step-size rule;
 rows N in {256, 512, 1024} fp64 and N=512 fp32, no default-experiment row.
 
-usage: tools/batch_bench.py [--quick] [--adaptive] [--only N,dtype,B [--once]]
+--seats S: the seat queue (BatchSolver(seats=S)).  With --only N,dtype,R the R members run as a queue of S seats -- the
+price of the queue per step is this row against R/S plain batches of S (--only N,dtype,S).  With --default N the
+default experiment (energy stop, ntmax 1e6) of --members M runs at grid size N three ways: groups of S (run_ensemble(
+batch=S)), one plain batch of all M, and one queue of S seats (batch=S, queue=True); 1 warm-up + 3 repetitions each,
+member-steps/s and end-to-end seconds.
+
+usage: tools/batch_bench.py [--quick] [--adaptive] [--only N,dtype,B [--once]] [--seats S] [--default N [--members M]]
     --quick: N=512 fp64 only, B in {1, 16}
     --only:  one batched row and nothing else, e.g. --only 512,float64,16; --once: a single call without warm-up or
              repetitions (what a kernel trace should hold)
@@ -72,9 +78,9 @@ def single(N, dtype):
     return STEPS / mean, STEPS / best
 
 
-def batched(N, B, dtype):
+def batched(N, B, dtype, seats=None):
     _, _, ps = members(N, B, dtype)
-    bs = BatchSolver(ps)
+    bs = BatchSolver(ps, seats=seats)
 
     def run():
         bs.prepare()
@@ -117,15 +123,42 @@ def default_experiment(B=64, batch=16):
     return out
 
 
+def default_queue(N, M, S):
+    """The default experiment of M members at grid size N: groups of S, one plain batch of M, one queue of S seats."""
+    init, ep, _ = members(N, M, ntmax=int(1e6), full_sim=False)
+    fn = lambda ids, p, rv, al, **kw: ex.run_batch_gpu(ids, p, rv, al, None, postprocess=False, **kw)
+    ways = ((f'batch={S}', dict(batch=S, batch_fn=fn)),
+            (f'batch={M} (one plain batch)', dict(batch=M, batch_fn=fn)),
+            (f'batch={S} queue', dict(batch=S, queue=True, queue_members=M, batch_fn=lambda *a: fn(*a, seats=S))))
+    for label, kw in ways:
+        steps = []
+
+        def run():
+            t0 = time.perf_counter()
+            recs = ex.run_ensemble(init, ep, **kw)
+            dt = time.perf_counter() - t0
+            steps[:] = [int(r[6]) for r in recs]
+            return dt
+        mean, best = timed(run)
+        print(f"default experiment N={N} energy stop, {M} members, {label}: {mean:7.2f} s ({best:7.2f}), "
+              f"{sum(steps)} member-steps ({sum(steps) / mean:9.0f}/s), stop steps {min(steps)}..{max(steps)}", flush=True)
+
+
 def main():
     global ADAPTIVE
     quick = '--quick' in sys.argv
     ADAPTIVE = '--adaptive' in sys.argv
     mode = 'adaptive step (delt_max = 4.9e-7/N), ' if ADAPTIVE else ''
+    seats = int(sys.argv[sys.argv.index('--seats') + 1]) if '--seats' in sys.argv else None
+    if '--default' in sys.argv:
+        M = int(sys.argv[sys.argv.index('--members') + 1]) if '--members' in sys.argv else 64
+        default_queue(int(sys.argv[sys.argv.index('--default') + 1]), M, seats or 16)
+        return
     if '--only' in sys.argv:
         N, dt, B = sys.argv[sys.argv.index('--only') + 1].split(',')
-        b_mean, b_best = batched(int(N), int(B), dt)
-        print(f"N={N} {dt} {mode}batch B={int(B):3d}: {b_mean:9.0f} ({b_best:9.0f}) member-steps/s", flush=True)
+        b_mean, b_best = batched(int(N), int(B), dt, seats)
+        what = f"batch B={int(B):3d}" if seats is None else f"queue R={int(B):3d} seats={seats:3d}"
+        print(f"N={N} {dt} {mode}{what}: {b_mean:9.0f} ({b_best:9.0f}) member-steps/s", flush=True)
         return
     rows = ([(512, 'float64')] if quick else
             [(256, 'float64'), (512, 'float64'), (1024, 'float64')] + ([] if ADAPTIVE else [(2048, 'float64')])
