@@ -363,42 +363,43 @@ class Batch:
         self._check(self.lib.chs_batch_prepare(self._h, _dptr(rows)), 'chs_batch_prepare')
         return rows
 
+    def _call(self, what, nsteps, issue):
+        """What `step_n` and `step_n_queued` share: the counts with their length check, `done` and `status`, the call
+        itself -- `issue(counts, n, done, status)` with the three arrays as the C ABI takes them, returning (rc, anything)
+        -- and its rc raised unless it is a member's NaN.  Returns (done, per-member rc, anything)."""
+        counts = np.ascontiguousarray([max(int(k), 0) for k in nsteps], dtype=np.int64)
+        if counts.size != self.B:
+            raise ValueError(f"nsteps needs {self.B} entries, got {counts.size}")
+        done = np.zeros(self.B, dtype=np.int64)
+        status = np.zeros(self.B, dtype=np.int32)
+        rc, extra = issue(counts, counts.ctypes.data_as(C.POINTER(C.c_int64)), done.ctypes.data_as(C.POINTER(C.c_int64)),
+                          status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc not in (CHS_OK, CHS_ENAN):
+            self._check(rc, what)
+        return done, [int(x) for x in status], extra
+
     def step_n(self, nsteps):
         """One literal call for every member: nsteps[m] iterations of member m.  Returns (list of rows[k_m, 9],
         list of per-member rc -- CHS_OK or CHS_ENAN, the rows then end with the NaN row)."""
-        n = np.ascontiguousarray([max(int(k), 0) for k in nsteps], dtype=np.int64)
-        if n.size != self.B:
-            raise ValueError(f"nsteps needs {self.B} entries, got {n.size}")
-        mx = int(n.max()) if n.size else 0
-        rows = np.empty((self.B, max(mx, 1), 9), dtype=np.float64)
-        done = np.zeros(self.B, dtype=np.int64)
-        status = np.zeros(self.B, dtype=np.int32)
-        rc = self.lib.chs_batch_step_n(self._h, n.ctypes.data_as(C.POINTER(C.c_int64)), 0, _dptr(rows),
-                                       done.ctypes.data_as(C.POINTER(C.c_int64)),
-                                       status.ctypes.data_as(C.POINTER(C.c_int32)))
-        if rc not in (CHS_OK, CHS_ENAN):
-            self._check(rc, 'chs_batch_step_n')
-        return [rows[m, :done[m]].copy() for m in range(self.B)], [int(x) for x in status]
+        def issue(counts, n, done, status):
+            mx = int(counts.max()) if counts.size else 0
+            rows = np.empty((self.B, max(mx, 1), 9), dtype=np.float64)
+            return self.lib.chs_batch_step_n(self._h, n, 0, _dptr(rows), done, status), rows
+        done, status, rows = self._call('chs_batch_step_n', nsteps, issue)
+        return [rows[m, :done[m]].copy() for m in range(self.B)], status
 
     def step_n_queued(self, nsteps, seats):
         """`step_n` with the members taking turns in `seats` seats on the device (chs_batch_step_n_queued): the same
         return value, bit for bit."""
-        n = np.ascontiguousarray([max(int(k), 0) for k in nsteps], dtype=np.int64)
-        if n.size != self.B:
-            raise ValueError(f"nsteps needs {self.B} entries, got {n.size}")
-        done = np.zeros(self.B, dtype=np.int64)
-        status = np.zeros(self.B, dtype=np.int32)
-        rc = self.lib.chs_batch_step_n_queued(self._h, int(seats), n.ctypes.data_as(C.POINTER(C.c_int64)), 0,
-                                              done.ctypes.data_as(C.POINTER(C.c_int64)),
-                                              status.ctypes.data_as(C.POINTER(C.c_int32)))
-        if rc not in (CHS_OK, CHS_ENAN):
-            self._check(rc, 'chs_batch_step_n_queued')
+        def issue(counts, n, done, status):
+            return self.lib.chs_batch_step_n_queued(self._h, int(seats), n, 0, done, status), None
+        done, status, _ = self._call('chs_batch_step_n_queued', nsteps, issue)
         rows = []
         for m in range(self.B):
             r = np.empty((int(done[m]), 9), dtype=np.float64)
             self._check(self.lib.chs_batch_member_rows(self._h, m, _dptr(r), int(done[m])), 'chs_batch_member_rows')
             rows.append(r)
-        return rows, [int(x) for x in status]
+        return rows, status
 
     def get_state(self, member):
         s = chs_state()

@@ -489,7 +489,7 @@ static int one_step(Engine* E, bool first, bool last) {
 // that stops after a thousand steps must not queue three million empty launches behind the stop.
 // The rows of finished batches are copied out of the device ring as they complete.
 
-static int copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to) {
+int chs_copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to) {
   // ring -> caller's array, rows [from, to); at most two pieces
   while (from < to) {
     const int64_t slot = from % E->rowsCap;
@@ -498,6 +498,25 @@ static int copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to) {
     CHS_HIP(hipMemcpy(rows + from * 9, E->dRows + slot * 9, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
     from += n;
   }
+  return CHS_OK;
+}
+
+// Did the energy rule or the time limit end a call of nsteps steps before its last step, with the fused row kernel
+// keeping U in registers?  Then hat_U is that of the last completed step and the field is to be rebuilt from it.
+bool chs_stopped_short(const Engine* E, const DevState& s, int64_t nsteps) {
+  return s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !E->storeU && s.rows_written < nsteps;
+}
+
+// U <- idctn(hat_U) of a call that stopped short (solver.py:197-199 breaks before U is updated, 242-251 returns the U
+// of the stopping step); s is the fetched state, which the device holds again afterwards
+int chs_rebuild_stopped_u(Engine* E, const DevState& s) {
+  int rc;
+  DevState r = s;
+  r.halt = 0;
+  CHS_HIP(hipMemcpy(E->dState, &r, sizeof r, hipMemcpyHostToDevice));
+  if ((rc = chs_fast_recover_u(E))) return rc;
+  CHS_HIP(hipStreamSynchronize(E->stream));
+  CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
   return CHS_OK;
 }
 
@@ -583,7 +602,7 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
         CHS_HIP(hipEventSynchronize(E->evPoll[prev]));
         const DevState& ps = E->hState[1 + prev];
         if (rows && ps.rows_written > copied) {
-          if ((rc = copy_rows_out(E, rows, copied, ps.rows_written))) return rc;
+          if ((rc = chs_copy_rows_out(E, rows, copied, ps.rows_written))) return rc;
           copied = ps.rows_written;
         }
         if (ps.halt) stopped = true;
@@ -624,17 +643,7 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
     E->dHat2 = (valid == E->dHatCall) ? other : E->dHatCall;
     E->dHat = valid;
   }
-  if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && fused && !E->storeU && s.rows_written < nsteps) {
-    // the energy rule or the time limit ended the call before its last step and the row kernel has
-    // been keeping U in registers: hat_U is that of the last completed step, rebuild the field from
-    // it (solver.py:197-199 breaks before U is updated, 242-251 returns the U of the stopping step)
-    DevState r = s;
-    r.halt = 0;
-    CHS_HIP(hipMemcpy(E->dState, &r, sizeof r, hipMemcpyHostToDevice));
-    if ((rc = chs_fast_recover_u(E))) return rc;
-    CHS_HIP(hipStreamSynchronize(E->stream));
-    CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
-  }
+  if (fused && chs_stopped_short(E, s, nsteps) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
   if (s.halt) E->hat_valid = false;  // (a deferred tail lets k_col run once past a NaN stop)
   if (nsteps > 0) E->resident = E->keepResident && !s.halt && s.rows_written >= nsteps;
   E->stateCached = true;  // (the recovery above leaves the device state equal to s)
@@ -645,7 +654,7 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
   if (staged) {
     memcpy(rows, E->hRows, sizeof(double) * 9 * (size_t)done);
   } else if (rows && done > copied) {
-    if ((rc = copy_rows_out(E, rows, copied, done))) return rc;
+    if ((rc = chs_copy_rows_out(E, rows, copied, done))) return rc;
   }
   if (rows) {
     // solver.py:230 `domtime = self.time_passed ** (1 / 3)` with the host libm

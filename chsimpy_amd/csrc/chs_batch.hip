@@ -26,11 +26,21 @@
 // k_seat_batch hands the seat of a member that has stopped or done its steps to the next one in member order, on the
 // device.  The host never learns who sits where: it issues every step's kernels for every seat and follows the members
 // through its polls of their states alone.
+//
+// Both entry points are "enter, own issue loop, finish" over one host record of the call (BatchCall): call_enter (the
+// checks, the adaptive/fused decision, every member's entry and record), call_poll and call_take_rows (the state fetch
+// behind a batch of steps and the rows that have completed) and call_finish (final states, the field of a member that
+// stopped short, rows, status) exist once.  The row copy and the rebuild of a stopped member's field are the single
+// handle's (chs_api.hip: chs_copy_rows_out, chs_stopped_short, chs_rebuild_stopped_u); the decisions that need no
+// device -- the queue's step bound, its last-step bookkeeping, the plain batch's batch_rule_fires -- are in
+// chs_batch_host.h, where a CPU test drives them.  The issue loops stay two: the plain batch knows who runs which step
+// and leaves launches out, the queue does not and issues everything, so one loop would change what one of them launches.
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "chs_batch_host.h"
 #include "chs_fast_kernels.h"
 
 // The batch's per-step bookkeeping: one workgroup per member running the single handle's tail body (chs_tail.h) with
@@ -261,64 +271,92 @@ extern "C" int chs_batch_prepare(chs_batch h, double* rows0) {
   return CHS_OK;
 }
 
-// rows of member i, [from, to) of its ring -> the caller's array
-static int copy_member_rows(Engine* E, double* rows, int64_t from, int64_t to) {
-  while (from < to) {
-    const int64_t slot = from % E->rowsCap;
-    int64_t n = to - from;
-    if (slot + n > E->rowsCap) n = E->rowsCap - slot;
-    CHS_HIP(hipMemcpy(rows + from * 9, E->dRows + slot * 9, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
-    from += n;
+// the device and pinned arrays of the seat queue, at the first queued call (and when a call asks for more seats)
+static int queue_buffers(Batch* b, int seats) {
+  const size_t nq = 1 + (size_t)b->B;
+  if (!b->dQueue) CHS_HIP(hipMalloc(&b->dQueue, sizeof(long long) * nq));
+  if (!b->hQueue) CHS_HIP(hipHostMalloc((void**)&b->hQueue, sizeof(long long) * 5 * nq, hipHostMallocDefault));
+  if (seats > b->seatCap) {
+    if (b->dSeat) { CHS_HIP(hipStreamSynchronize(b->stream)); CHS_HIP(hipFree(b->dSeat)); b->dSeat = nullptr; b->seatCap = 0; }
+    CHS_HIP(hipMalloc(&b->dSeat, sizeof(BatchMember) * (size_t)seats));
+    b->seatCap = seats;
   }
   return CHS_OK;
 }
 
-// chs_step_n of every member as a literal solve_or_resume call (hat_U = dctn(U) on entry, U stored at the end), the
-// steps of all members issued together.  As in chs_step_n the steps go out in batches, and behind every batch the
-// members' states are fetched; once every member that still has steps to do has halted nothing more is issued.
-extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flags, double* rows, int64_t* steps_done,
-                                int32_t* status) {
-  Batch* b = as_batch(h);
-  if (!b || !nsteps || !steps_done || !status) return bad("chs_batch_step_n: null argument");
-  if (flags != 0) return bad("chs_batch_step_n: flags is reserved and must be 0");
+// ---------------------------------------------------------------------------
+// One call of the batch, plain or queued: what chs_batch_step_n and chs_batch_step_n_queued share.  Each of them is
+// call_enter, its own issue loop with call_poll behind every batch of steps, call_finish.
+// ---------------------------------------------------------------------------
+namespace {
+struct BatchCall {
+  Batch* b;
+  const char* who;            // the entry point's name, for the error texts
+  const int64_t* nsteps;
+  int64_t* steps_done;
+  int32_t* status;
+  double* rows;               // the plain batch: the caller's [B][maxn][9]; the queue's rows go to Batch::qRows
+  bool queued;                // chs_batch_step_n_queued: the members take turns in ...
+  int seats = 0;              // ... this many seats (min(seats asked for, B))
+  int running = 0;            // members with steps to do
+  int64_t maxn = 0;           // the longest call
+  bool adaptive = false;      // an adaptive batch (all members or none: chs_batch_create)
+  bool fused = true;          // ... whose row kernel adds up the step-size integrand
+  int batch_steps = 1024;     // steps between two polls
+  std::vector<long long> cs0; // the members' step counters at the entry, where the host knows them
+  std::vector<int64_t> copied;  // rows of each member that its destination holds already
+  int poll = 0;
+};
+
+// The checks of the arguments, then the entry of every member that runs -- re-armed loop, hat_U = dctn(U) and the first
+// step's row transform of EnergieEut(U): the single handle's code on the shared stream -- and the members' records, on
+// the device in Batch::dMem.  `seats`: what the caller of a queued call asked for.
+int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
+  Batch* b = c.b;
+  const std::string who = c.who;
+  if (!b || !c.nsteps || !c.steps_done || !c.status) return bad(who + ": null argument");
+  if (flags != 0) return bad(who + ": flags is reserved and must be 0");
+  if (c.queued && seats < 1) return bad(who + ": seats must be >= 1");
   const int B = b->B;
-  int64_t maxn = 0;
+  if (c.queued) c.seats = seats < B ? seats : B;
   for (int i = 0; i < B; ++i) {
-    if (nsteps[i] > 0 && !b->m[i]->prepared) {
-      chs_set_error("chs_batch_step_n: member " + std::to_string(i) + " not prepared (solver.py:139)");
+    if (c.nsteps[i] > 0 && !b->m[i]->prepared) {
+      chs_set_error(who + ": member " + std::to_string(i) + " not prepared (solver.py:139)");
       return CHS_ESTATE;
     }
-    if (nsteps[i] > maxn) maxn = nsteps[i];
+    if (c.nsteps[i] > c.maxn) c.maxn = c.nsteps[i];
+    c.running += c.nsteps[i] > 0;
   }
-  if (maxn > 0 && !rows) return bad("chs_batch_step_n: rows is null");
+  if (!c.queued && c.maxn > 0 && !c.rows) return bad(who + ": rows is null");
   CHS_HIP(hipSetDevice(b->device));
   int rc;
-  int batch_steps = 1024;
-  // an adaptive batch (all members or none: chs_batch_create); `fused`: the row kernel adds up the step-size integrand
-  bool adaptive = false, fused = true;
+  if (c.queued) {
+    if ((rc = queue_buffers(b, c.seats))) return rc;
+    b->qRows.assign((size_t)B, std::vector<double>());
+  }
   for (int i = 0; i < B; ++i) {
     const Engine* E = b->m[i];
-    adaptive |= E->dc.adaptive_time != 0;
-    fused &= E->fusedAdapt && E->dPartColRows != nullptr;
+    c.adaptive |= E->dc.adaptive_time != 0;
+    c.fused &= E->fusedAdapt && E->dPartColRows != nullptr;
   }
-  fused &= adaptive;
-  std::vector<long long> cs0((size_t)B, -1);   // the members' step counters at the entry, where the host knows them
-  // entry of every member that runs: re-armed loop, hat_U = dctn(U) and the first step's row transform of EnergieEut(U)
+  c.fused &= c.adaptive;
+  c.cs0.assign((size_t)B, -1);
+  c.copied.assign((size_t)B, 0);
   for (int i = 0; i < B; ++i) {
     Engine* E = b->m[i];
     BatchMember& r = b->hMem[(size_t)i];
     std::memset((void*)&r, 0, sizeof r);
-    const int64_t n = nsteps[i] > 0 ? nsteps[i] : 0;
+    const int64_t n = c.nsteps[i] > 0 ? c.nsteps[i] : 0;
     r.nsteps = n;
-    steps_done[i] = 0;
-    status[i] = CHS_OK;
+    c.steps_done[i] = 0;
+    c.status[i] = CHS_OK;
     r.st = E->dState;   // (read by every batched kernel: rows_written >= nsteps = 0 keeps the member out)
-    if (n == 0) continue;   // sits the call out: state and field stay as they are
+    if (n == 0) continue;   // sits the call out (a queue never seats it): state and field stay as they are
     E->stateCached = false; E->resident = false; E->keepResident = false;
     E->tailDeferred = false; E->tailGated = false; E->preRider = false;
-    E->storeU = adaptive && !fused;   // (the sweep of U needs the field of every step: chs_fast_step)
-    cs0[(size_t)i] = E->csHost;
-    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) batch_steps = E->batchSteps < batch_steps ? E->batchSteps : batch_steps;
+    E->storeU = c.adaptive && !c.fused;   // (the sweep of U needs the field of every step: chs_fast_step)
+    c.cs0[(size_t)i] = E->csHost;
+    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
     if ((rc = chs_launch_call_begin(E))) return rc;
     if ((rc = chs_fast_enter_fused(E))) return rc;   // (selects the partial-sum set the whole call uses)
     E->hat_valid = true;
@@ -332,40 +370,133 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     r.tail[0].pre_only = 1;
     r.tail[1] = chs_tail_args(E, -1, 1);
     r.tail[2] = chs_tail_args(E, -1, 0);
-    if (adaptive) {
+    if (c.adaptive) {
       // the first step's time-step control as the single handle runs it: the integrand's column sums from a sweep of
       // U (the rule looks at the counter as the previous call left it), then k_pre -- once per call
-      if (fused && (rc = chs_colmin_batch_buffers(E, &r))) return rc;
+      if (c.fused && (rc = chs_colmin_batch_buffers(E, &r))) return rc;
       if ((rc = chs_launch_mu_colsums(E, 0))) return rc;
       if ((rc = chs_launch_pre(E))) return rc;
     }
   }
   if (const char* bs = getenv("CHS_BATCH_STEPS")) {   // (the test hook of chs_step_n: small batches exercise the polls)
     const long v = atol(bs);
-    if (v >= 1 && v <= 8192) batch_steps = (int)v;
+    if (v >= 1 && v <= 8192) c.batch_steps = (int)v;
   }
   CHS_HIP(hipMemcpyAsync(b->dMem, b->hMem.data(), sizeof(BatchMember) * (size_t)B, hipMemcpyHostToDevice, b->stream));
+  return CHS_OK;
+}
+
+// rows [copied, w) of member i out of its ring to where the call's rows go
+int call_take_rows(BatchCall& c, int i, int64_t w) {
+  int64_t& have = c.copied[(size_t)i];
+  if (w <= have) return CHS_OK;
+  double* dst;
+  if (c.queued) {
+    std::vector<double>& v = c.b->qRows[(size_t)i];
+    v.resize((size_t)w * 9);
+    dst = v.data();
+  } else {
+    dst = c.rows + (size_t)i * c.maxn * 9;
+  }
+  const int rc = chs_copy_rows_out(c.b->m[i], dst, have, w);
+  have = w;
+  return rc;
+}
+
+// Behind a batch of steps: the states of the members that `want` names are fetched into the pinned slot of this poll
+// (and what `also` adds to it), and the poll before this one is waited for -- the device is busy with the steps just
+// issued then, so it never idles.  *seen: the slot of that poll in hPoll (its members' rows that have completed are
+// taken here), 0 while there is none; the caller draws its own conclusions from the states.
+template <class Want, class Also>
+int call_poll(BatchCall& c, Want&& want, Also&& also, int* seen) {
+  Batch* b = c.b;
+  const int B = b->B;
+  const int slot = 1 + (c.poll & 3);
+  for (int i = 0; i < B; ++i)
+    if (want(i))
+      CHS_HIP(hipMemcpyAsync(&b->hPoll[(size_t)slot * B + i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
+  int rc;
+  if ((rc = also(slot))) return rc;
+  CHS_HIP(hipEventRecord(b->evPoll[c.poll & 3], b->stream));
+  *seen = 0;
+  if (c.poll >= 1) {
+    const int prev = (c.poll - 1) & 3;
+    CHS_HIP(hipEventSynchronize(b->evPoll[prev]));
+    *seen = 1 + prev;
+  }
+  ++c.poll;
+  return CHS_OK;
+}
+
+// rows of member i that the state `ps` of a poll shows as completed
+int call_take_polled(BatchCall& c, int i, const DevState& ps) {
+  return call_take_rows(c, i, ps.rows_written < c.nsteps[i] ? ps.rows_written : c.nsteps[i]);
+}
+
+// The end of a call: the members' states, the field of a member that stopped before its last step, what the host keeps
+// of the state, the remaining rows and the per-member status.
+int call_finish(BatchCall& c) {
+  Batch* b = c.b;
+  const int B = b->B;
+  int rc;
+  for (int i = 0; i < B; ++i)
+    if (c.nsteps[i] > 0)
+      CHS_HIP(hipMemcpyAsync(&b->hPoll[i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
+  CHS_HIP(hipStreamSynchronize(b->stream));
+  bool any_nan = false;
+  for (int i = 0; i < B; ++i) {
+    if (c.nsteps[i] <= 0) continue;
+    Engine* E = b->m[i];
+    const DevState s = b->hPoll[i];
+    if (c.queued && !s.halt && s.rows_written < c.nsteps[i]) {   // (a queue's step bound or last-step pair went wrong)
+      chs_set_error(std::string(c.who) + ": member " + std::to_string(i) + " was left with steps to do");
+      return CHS_ESTATE;
+    }
+    // its row kernel has been keeping U in registers -- the member's own arrays, whoever has its seat by now
+    if (chs_stopped_short(E, s, c.nsteps[i]) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
+    if (s.halt) E->hat_valid = false;
+    E->csHost = s.computed_steps;
+    const int64_t done = s.rows_written < c.nsteps[i] ? s.rows_written : c.nsteps[i];
+    c.steps_done[i] = done;
+    if ((rc = call_take_rows(c, i, done))) return rc;
+    double* mr = c.queued ? b->qRows[(size_t)i].data() : c.rows + (size_t)i * c.maxn * 9;
+    // solver.py:230 `domtime = self.time_passed ** (1 / 3)` with the host libm
+    for (int64_t k = 0; k < done; ++k) mr[k * 9 + 4] = pow(mr[k * 9 + 4], 1.0 / 3.0);
+    if (s.nan_flag) { c.status[i] = CHS_ENAN; any_nan = true; }
+  }
+  if (any_nan) {
+    chs_set_error("NaN in a recorded scalar (timedata.py:10) of a member: U left (0,1)");
+    return CHS_ENAN;
+  }
+  return CHS_OK;
+}
+}  // namespace
+
+// chs_step_n of every member as a literal solve_or_resume call (hat_U = dctn(U) on entry, U stored at the end), the
+// steps of all members issued together.  As in chs_step_n the steps go out in batches, and behind every batch the
+// members' states are fetched; once every member that still has steps to do has halted nothing more is issued.
+// The host knows who runs which step: it leaves out the launches that no member needs (`go_on`, `last`, batch_rule_fires).
+extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flags, double* rows, int64_t* steps_done,
+                                int32_t* status) {
+  BatchCall c{as_batch(h), "chs_batch_step_n", nsteps, steps_done, status, rows, false};
+  int rc;
+  if ((rc = call_enter(c, flags, 0))) return rc;
+  Batch* b = c.b;
+  const int B = b->B;
+  const int64_t maxn = c.maxn;
+  const bool adaptive = c.adaptive, fused = c.fused;
   Engine* E0 = b->m[0];
   FastPlan* P = (FastPlan*)E0->dTw;
-  std::vector<int64_t> copied((size_t)B, 0);
   if (maxn > 0 && !adaptive) {
     if ((rc = launch_tail(b->stream, b->dMem, B, P->col_threads, false, 1))) return rc;
   }
-  // does member i's step-size rule fire behind step s of this call?  (as far as the host can tell: an unknown counter fires)
-  auto fires = [&](int i, int64_t s) {
-    if (s >= nsteps[i] - 1) return false;           // no step behind s: no time-step control
-    if (cs0[(size_t)i] < 0) return true;
-    const long long cs_next = cs0[(size_t)i] + s + 1;   // (chs_tail.h: cs_next; a halted member's kernels are no-ops)
-    return cs_next > 500 && (cs_next % 2) == 0;
-  };
   const int fuse_mode = fused ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED;
   const int store_u = (adaptive && !fused) ? 1 : 0;
   int64_t issued = 0;
-  int poll = 0;
   bool stopped = false;
   while (issued < maxn && !stopped) {
     int64_t nb = maxn - issued;
-    if (nb > batch_steps) nb = batch_steps;
+    if (nb > c.batch_steps) nb = c.batch_steps;
     for (int64_t s = issued; s < issued + nb; ++s) {
       bool go_on = false, last = false;
       for (int i = 0; i < B; ++i) {
@@ -379,11 +510,11 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
         // the column minimum of the coming step's integrand, for the members whose rule fires (the kernels check again)
         if (fused) {
           bool any = false;
-          for (int i = 0; i < B; ++i) any |= fires(i, s);
+          for (int i = 0; i < B; ++i) any |= batch_rule_fires(c.cs0[(size_t)i], nsteps[i], s);
           if (any && (rc = chs_launch_colmin_rows_batch(b->stream, b->dMem, B, b->N, b->dtype == CHS_F32))) return rc;
         } else {
           for (int i = 0; i < B; ++i)
-            if (fires(i, s) && (rc = chs_launch_mu_colsums(b->m[i], 1))) return rc;
+            if (batch_rule_fires(c.cs0[(size_t)i], nsteps[i], s) && (rc = chs_launch_mu_colsums(b->m[i], 1))) return rc;
         }
       }
       // (the last-step records first: a member whose record the other launch writes moves on to its last step)
@@ -392,177 +523,48 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
     }
     issued += nb;
     if (issued < maxn) {
-      const int slot = 1 + (poll & 3);
-      for (int i = 0; i < B; ++i)
-        if (nsteps[i] > 0)
-          CHS_HIP(hipMemcpyAsync(&b->hPoll[(size_t)slot * B + i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
-      CHS_HIP(hipEventRecord(b->evPoll[poll & 3], b->stream));
-      if (poll >= 1) {
-        const int prev = (poll - 1) & 3;
-        CHS_HIP(hipEventSynchronize(b->evPoll[prev]));
-        const DevState* ps = &b->hPoll[(size_t)(1 + prev) * B];
+      int seen = 0;
+      if ((rc = call_poll(c, [&](int i) { return nsteps[i] > 0; }, [](int) { return (int)CHS_OK; }, &seen))) return rc;
+      if (seen) {
+        const DevState* ps = &b->hPoll[(size_t)seen * B];
         bool all = true;
         for (int i = 0; i < B; ++i) {
           if (nsteps[i] <= 0) continue;
-          const int64_t w = ps[i].rows_written < nsteps[i] ? ps[i].rows_written : nsteps[i];
-          if (w > copied[(size_t)i]) {
-            if ((rc = copy_member_rows(b->m[i], rows + (size_t)i * maxn * 9, copied[(size_t)i], w))) return rc;
-            copied[(size_t)i] = w;
-          }
+          if ((rc = call_take_polled(c, i, ps[i]))) return rc;
           // (the poll is two batches behind: a member that was running then and has steps left now is still going)
           if (!ps[i].halt && nsteps[i] > issued) all = false;
         }
         if (all) stopped = true;
       }
-      ++poll;
     }
   }
-  for (int i = 0; i < B; ++i)
-    if (nsteps[i] > 0)
-      CHS_HIP(hipMemcpyAsync(&b->hPoll[i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
-  CHS_HIP(hipStreamSynchronize(b->stream));
-  bool any_nan = false;
-  for (int i = 0; i < B; ++i) {
-    if (nsteps[i] <= 0) continue;
-    Engine* E = b->m[i];
-    const DevState s = b->hPoll[i];
-    if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !E->storeU && s.rows_written < nsteps[i]) {
-      // the energy rule or the time limit ended this member's call before its last step: its row kernel has been
-      // keeping U in registers and hat_U is that of the last completed step -- the field is rebuilt from it (run_steps)
-      DevState r = s;
-      r.halt = 0;
-      CHS_HIP(hipMemcpy(E->dState, &r, sizeof r, hipMemcpyHostToDevice));
-      if ((rc = chs_fast_recover_u(E))) return rc;
-      CHS_HIP(hipStreamSynchronize(b->stream));
-      CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
-    }
-    if (s.halt) E->hat_valid = false;
-    E->csHost = s.computed_steps;
-    int64_t done = s.rows_written < nsteps[i] ? s.rows_written : nsteps[i];
-    steps_done[i] = done;
-    double* mr = rows + (size_t)i * maxn * 9;
-    if (done > copied[(size_t)i] && (rc = copy_member_rows(E, mr, copied[(size_t)i], done))) return rc;
-    // solver.py:230 `domtime = self.time_passed ** (1 / 3)` with the host libm
-    for (int64_t k = 0; k < done; ++k) mr[k * 9 + 4] = pow(mr[k * 9 + 4], 1.0 / 3.0);
-    if (s.nan_flag) { status[i] = CHS_ENAN; any_nan = true; }
-  }
-  if (any_nan) {
-    chs_set_error("NaN in a recorded scalar (timedata.py:10) of a member: U left (0,1)");
-    return CHS_ENAN;
-  }
-  return CHS_OK;
+  return call_finish(c);
 }
 
 // ---------------------------------------------------------------------------
 // The seat queue: chs_batch_step_n over `seats` records that the members of the batch take turns in.
 // ---------------------------------------------------------------------------
-static int queue_buffers(Batch* b, int seats) {
-  const size_t nq = 1 + (size_t)b->B;
-  if (!b->dQueue) CHS_HIP(hipMalloc(&b->dQueue, sizeof(long long) * nq));
-  if (!b->hQueue) CHS_HIP(hipHostMalloc((void**)&b->hQueue, sizeof(long long) * 5 * nq, hipHostMallocDefault));
-  if (seats > b->seatCap) {
-    if (b->dSeat) { CHS_HIP(hipStreamSynchronize(b->stream)); CHS_HIP(hipFree(b->dSeat)); b->dSeat = nullptr; b->seatCap = 0; }
-    CHS_HIP(hipMalloc(&b->dSeat, sizeof(BatchMember) * (size_t)seats));
-    b->seatCap = seats;
-  }
-  return CHS_OK;
-}
 
-// The global step count of the call when no member stops early: the members take the seats in member order, a seat
-// changes hands in front of an even step (k_seat_batch).  A member that stops early only lets the ones behind it start
-// sooner, so this bounds the steps to issue; with as many seats as members it is the largest nsteps.
-static int64_t queue_step_bound(const int64_t* nsteps, int R, int seats) {
-  std::vector<int64_t> free_at((size_t)seats, 0);
-  int64_t bound = 0;
-  for (int i = 0; i < R; ++i) {
-    if (nsteps[i] <= 0) continue;
-    size_t k = 0;
-    for (size_t j = 1; j < free_at.size(); ++j) if (free_at[j] < free_at[k]) k = j;
-    const int64_t start = free_at[k] + (free_at[k] & 1);
-    free_at[k] = start + nsteps[i];
-    if (free_at[k] > bound) bound = free_at[k];
-  }
-  return bound;
-}
-
-// chs_batch_step_n with the members taking turns in `seats` seats: the entry of every member up front (the single
-// handle's code, as in chs_batch_step_n), then every step kernel launched over the seats; k_seat_batch hands a seat
+// chs_batch_step_n with the members taking turns in `seats` seats: the entry of every member up front (call_enter: the
+// records are those of the waiting members), then every step kernel launched over the seats; k_seat_batch hands a seat
 // on.  The host does not know who sits where, so it leaves nothing out that a seated member might need: the fused row
 // kernel, the normal tail and (adaptive) the reduction go out on every step, the last-step pair from the first step on
-// at which the call of some unfinished member may end.  The kernels decide per member, as they always did.
+// at which the call of some unfinished member may end (QueueMembers, chs_batch_host.h).  The kernels decide per member,
+// as they always did.
 extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t* nsteps, int32_t flags,
                                        int64_t* steps_done, int32_t* status) {
-  Batch* b = as_batch(h);
-  if (!b || !nsteps || !steps_done || !status) return bad("chs_batch_step_n_queued: null argument");
-  if (flags != 0) return bad("chs_batch_step_n_queued: flags is reserved and must be 0");
-  if (seats < 1) return bad("chs_batch_step_n_queued: seats must be >= 1");
-  const int R = b->B;
-  const int S = seats < R ? seats : R;
-  int running = 0;
-  for (int i = 0; i < R; ++i) {
-    if (nsteps[i] > 0 && !b->m[i]->prepared) {
-      chs_set_error("chs_batch_step_n_queued: member " + std::to_string(i) + " not prepared (solver.py:139)");
-      return CHS_ESTATE;
-    }
-    running += nsteps[i] > 0;
-  }
-  CHS_HIP(hipSetDevice(b->device));
+  BatchCall c{as_batch(h), "chs_batch_step_n_queued", nsteps, steps_done, status, nullptr, true};
   int rc;
-  if ((rc = queue_buffers(b, S))) return rc;
-  int batch_steps = 1024;
-  bool adaptive = false, fused = true;
-  for (int i = 0; i < R; ++i) {
-    const Engine* E = b->m[i];
-    adaptive |= E->dc.adaptive_time != 0;
-    fused &= E->fusedAdapt && E->dPartColRows != nullptr;
-  }
-  fused &= adaptive;
-  b->qRows.assign((size_t)R, std::vector<double>());
-  // entry of every member that runs, exactly as in chs_batch_step_n: the records are those of the waiting members
-  for (int i = 0; i < R; ++i) {
-    Engine* E = b->m[i];
-    BatchMember& r = b->hMem[(size_t)i];
-    std::memset((void*)&r, 0, sizeof r);
-    const int64_t n = nsteps[i] > 0 ? nsteps[i] : 0;
-    r.nsteps = n;
-    steps_done[i] = 0;
-    status[i] = CHS_OK;
-    r.st = E->dState;
-    if (n == 0) continue;   // sits the call out: never seated, state and field stay as they are
-    E->stateCached = false; E->resident = false; E->keepResident = false;
-    E->tailDeferred = false; E->tailGated = false; E->preRider = false;
-    E->storeU = adaptive && !fused;
-    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) batch_steps = E->batchSteps < batch_steps ? E->batchSteps : batch_steps;
-    if ((rc = chs_launch_call_begin(E))) return rc;
-    if ((rc = chs_fast_enter_fused(E))) return rc;
-    E->hat_valid = true;
-    r.dc = E->dc;
-    r.T1 = E->dT1;
-    r.T2 = E->dT1;
-    r.hat = E->dHat;
-    r.U = E->dU;
-    r.partDiag = E->dPartDiag; r.partMu = E->dPartMu; r.partRa = E->dPartRa; r.partE2 = E->dPartE2;
-    r.tail[0] = chs_tail_args(E, -1, 1);
-    r.tail[0].pre_only = 1;
-    r.tail[1] = chs_tail_args(E, -1, 1);
-    r.tail[2] = chs_tail_args(E, -1, 0);
-    if (adaptive) {
-      if (fused && (rc = chs_colmin_batch_buffers(E, &r))) return rc;
-      if ((rc = chs_launch_mu_colsums(E, 0))) return rc;
-      if ((rc = chs_launch_pre(E))) return rc;
-    }
-  }
-  if (const char* bs = getenv("CHS_BATCH_STEPS")) {
-    const long v = atol(bs);
-    if (v >= 1 && v <= 8192) batch_steps = (int)v;
-  }
+  if ((rc = call_enter(c, flags, seats))) return rc;
+  Batch* b = c.b;
+  const int R = b->B, S = c.seats, running = c.running;
+  const bool adaptive = c.adaptive, fused = c.fused;
   // every seat vacant (no step in the call, somebody's state to look at); the queue at member 0, nobody seated
   b->hSeat.assign((size_t)S, BatchMember());
   for (BatchMember& v : b->hSeat) { std::memset((void*)&v, 0, sizeof v); v.st = b->m[0]->dState; }
   b->hQueue0.assign(1 + (size_t)R, -1);
   b->hQueue0[0] = 0;
   const size_t nq = 1 + (size_t)R;
-  CHS_HIP(hipMemcpyAsync(b->dMem, b->hMem.data(), sizeof(BatchMember) * (size_t)R, hipMemcpyHostToDevice, b->stream));
   CHS_HIP(hipMemcpyAsync(b->dSeat, b->hSeat.data(), sizeof(BatchMember) * (size_t)S, hipMemcpyHostToDevice, b->stream));
   CHS_HIP(hipMemcpyAsync(b->dQueue, b->hQueue0.data(), sizeof(long long) * nq, hipMemcpyHostToDevice, b->stream));
   Engine* E0 = b->m[0];
@@ -578,44 +580,16 @@ extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t
   }
   const int fuse_mode = fused ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED;
   const int store_u = (adaptive && !fused) ? 1 : 0;
-  std::vector<int64_t> copied((size_t)R, 0);
-  // The last-step pair of member i belongs to step seated + nsteps[i] - 1 exactly: without it the member would stand at
-  // its last step while k_col goes on updating its hat_U.  While the seating step is not known, seated[i] is a lower
-  // bound of it (0, then what the polls show) and the pair goes out on EVERY step from seated[i] + nsteps[i] - 1 on;
-  // once a poll has shown the step (`known`), on that one step.  The first `seats` members that run are seated in front
-  // of step 0.
-  std::vector<int64_t> seated((size_t)R, 0);
-  std::vector<char> known((size_t)R, 0), served((size_t)R, 0);
-  std::vector<char> finished((size_t)R, 0);       // (as far as the polls have shown)
-  for (int i = 0, k = 0; i < R; ++i) {
-    finished[(size_t)i] = nsteps[i] <= 0;
-    if (nsteps[i] > 0 && k++ < S) known[(size_t)i] = 1;
-  }
+  QueueMembers qm(nsteps, R, S);
   bool all_seated = running <= S;                 // nobody waits (any more): no seat changes hands
-  // rows [copied, w) of member i out of its ring into its host array
-  auto take_rows = [&](int i, int64_t w) {
-    if (w <= copied[(size_t)i]) return (int)CHS_OK;
-    std::vector<double>& v = b->qRows[(size_t)i];
-    v.resize((size_t)w * 9);
-    const int r = copy_member_rows(b->m[i], v.data(), copied[(size_t)i], w);
-    copied[(size_t)i] = w;
-    return r;
-  };
   int64_t issued = 0;
   int64_t poll_issued[4] = {0, 0, 0, 0};
-  int poll = 0;
   bool stopped = false;
   while (issued < bound && !stopped) {
     int64_t nb = bound - issued;
-    if (nb > batch_steps) nb = batch_steps;
+    if (nb > c.batch_steps) nb = c.batch_steps;
     for (int64_t s = issued; s < issued + nb; ++s) {
-      // may the call of an unfinished member end with this step?
-      bool last = false;
-      for (int i = 0; i < R; ++i) {
-        if (finished[(size_t)i] || served[(size_t)i] || s < seated[(size_t)i] + nsteps[i] - 1) continue;
-        last = true;
-        served[(size_t)i] = known[(size_t)i];
-      }
+      const bool last = qm.last_pair(s);   // may the call of an unfinished member end with this step?
       if ((rc = P->col_batch(E0, b->stream, b->dSeat, S, (s & 1) ? 1 : 0))) return rc;
       if ((rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, fuse_mode, store_u))) return rc;
       if (last && (rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, ROW_INV_DIAG, 1))) return rc;
@@ -626,7 +600,7 @@ extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t
           // (the sweep of U works on the member's own arrays, seated or not: what it leaves for a member in waiting is
           // written again behind that member's own row kernel before its tail reads it)
           for (int i = 0; i < R; ++i)
-            if (!finished[(size_t)i] && (rc = chs_launch_mu_colsums(b->m[i], 1))) return rc;
+            if (!qm.finished[(size_t)i] && (rc = chs_launch_mu_colsums(b->m[i], 1))) return rc;
         }
       }
       // (the last-step records first, as in chs_batch_step_n)
@@ -639,73 +613,28 @@ extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t
     }
     issued += nb;
     if (issued < bound) {
-      const int slot = 1 + (poll & 3);
-      for (int i = 0; i < R; ++i)
-        if (!finished[(size_t)i])
-          CHS_HIP(hipMemcpyAsync(&b->hPoll[(size_t)slot * R + i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
-      CHS_HIP(hipMemcpyAsync(b->hQueue + (size_t)slot * nq, b->dQueue, sizeof(long long) * nq, hipMemcpyDeviceToHost, b->stream));
-      CHS_HIP(hipEventRecord(b->evPoll[poll & 3], b->stream));
-      poll_issued[poll & 3] = issued;
-      if (poll >= 1) {
-        const int prev = (poll - 1) & 3;
-        CHS_HIP(hipEventSynchronize(b->evPoll[prev]));
-        const DevState* ps = &b->hPoll[(size_t)(1 + prev) * R];
-        const long long* pq = b->hQueue + (size_t)(1 + prev) * nq;
+      poll_issued[c.poll & 3] = issued;
+      int seen = 0;
+      auto fetch_queue = [&](int slot) {
+        CHS_HIP(hipMemcpyAsync(b->hQueue + (size_t)slot * nq, b->dQueue, sizeof(long long) * nq, hipMemcpyDeviceToHost, b->stream));
+        return (int)CHS_OK;
+      };
+      if ((rc = call_poll(c, [&](int i) { return !qm.finished[(size_t)i]; }, fetch_queue, &seen))) return rc;
+      if (seen) {
+        const DevState* ps = &b->hPoll[(size_t)seen * R];
+        const long long* pq = b->hQueue + (size_t)seen * nq;
         bool all = true;
         for (int i = 0; i < R; ++i) {
-          if (finished[(size_t)i]) continue;   // (its slot was not fetched; its rows were taken when it was found finished)
-          const int64_t w = ps[i].rows_written < nsteps[i] ? ps[i].rows_written : nsteps[i];
-          if ((rc = take_rows(i, w))) return rc;
-          if (ps[i].halt || ps[i].rows_written >= nsteps[i]) finished[(size_t)i] = 1;
-          else all = false;
-          // seated by then: the step is known; still waiting: not before the steps that had been issued
-          if (pq[1 + i] >= 0) { seated[(size_t)i] = (int64_t)pq[1 + i]; known[(size_t)i] = 1; }
-          else if (!known[(size_t)i]) seated[(size_t)i] = poll_issued[prev];
+          if (qm.finished[(size_t)i]) continue;   // (its slot was not fetched; its rows were taken when it was found finished)
+          if ((rc = call_take_polled(c, i, ps[i]))) return rc;
+          if (qm.poll(i, ps[i].halt != 0, ps[i].rows_written, pq[1 + i], poll_issued[seen - 1])) all = false;
         }
         if (pq[0] >= R) all_seated = true;
         if (all) stopped = true;
       }
-      ++poll;
     }
   }
-  for (int i = 0; i < R; ++i)
-    if (nsteps[i] > 0)
-      CHS_HIP(hipMemcpyAsync(&b->hPoll[i], b->m[i]->dState, sizeof(DevState), hipMemcpyDeviceToHost, b->stream));
-  CHS_HIP(hipStreamSynchronize(b->stream));
-  bool any_nan = false;
-  for (int i = 0; i < R; ++i) {
-    if (nsteps[i] <= 0) continue;
-    Engine* E = b->m[i];
-    const DevState s = b->hPoll[i];
-    if (!s.halt && s.rows_written < nsteps[i]) {
-      chs_set_error("chs_batch_step_n_queued: member " + std::to_string(i) + " was left with steps to do");
-      return CHS_ESTATE;
-    }
-    if (s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !E->storeU && s.rows_written < nsteps[i]) {
-      // stopped before its last step: the field is rebuilt from hat_U of the last completed step (chs_batch_step_n) --
-      // the member's own arrays, whoever has its seat by now
-      DevState r = s;
-      r.halt = 0;
-      CHS_HIP(hipMemcpy(E->dState, &r, sizeof r, hipMemcpyHostToDevice));
-      if ((rc = chs_fast_recover_u(E))) return rc;
-      CHS_HIP(hipStreamSynchronize(b->stream));
-      CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
-    }
-    if (s.halt) E->hat_valid = false;
-    E->csHost = s.computed_steps;
-    const int64_t done = s.rows_written < nsteps[i] ? s.rows_written : nsteps[i];
-    steps_done[i] = done;
-    if ((rc = take_rows(i, done))) return rc;
-    std::vector<double>& mr = b->qRows[(size_t)i];
-    // solver.py:230 `domtime = self.time_passed ** (1 / 3)` with the host libm
-    for (int64_t k = 0; k < done; ++k) mr[(size_t)k * 9 + 4] = pow(mr[(size_t)k * 9 + 4], 1.0 / 3.0);
-    if (s.nan_flag) { status[i] = CHS_ENAN; any_nan = true; }
-  }
-  if (any_nan) {
-    chs_set_error("NaN in a recorded scalar (timedata.py:10) of a member: U left (0,1)");
-    return CHS_ENAN;
-  }
-  return CHS_OK;
+  return call_finish(c);
 }
 
 // rows of member `member` from the last chs_batch_step_n_queued: n = its steps_done

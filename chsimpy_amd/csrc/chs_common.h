@@ -359,6 +359,11 @@ int chs_direct_dct2d(Engine* E, const void* in, void* out, void* tmp, bool inver
 // ---- fast engine (chs_fast.hip) ---------------------------------------------
 bool chs_fast_supported(int N, int dtype);
 int chs_fast_recover_u(Engine* E);  // U <- idctn(hat_U): the field of the last completed step
+// (chs_api.hip, shared by chs_step_n and the batch) a call that the energy rule or the time limit ended before its last
+// step: the test, and the rebuild of the field through chs_fast_recover_u around the fetched state s
+bool chs_stopped_short(const Engine* E, const DevState& s, int64_t nsteps);
+int chs_rebuild_stopped_u(Engine* E, const DevState& s);
+int chs_copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to);  // rows [from, to) of the ring -> rows[from*9 ...]
 int chs_fast_init(Engine* E);
 void chs_fast_free(Engine* E);
 int chs_fast_dct2d(Engine* E, const void* in, void* out, bool inverse);  // natural in/out (tests)

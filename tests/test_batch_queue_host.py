@@ -1,8 +1,10 @@
 """CPU tests of the seat queue (include/chs_hip.h chs_batch_step_n_queued / chs_batch_member_rows,
 ``BatchSolver(seats=S)``, ``run_ensemble(batch=B, queue=True)``): bindings, host-side validation and how an ensemble's
-runs are dealt to queues.  Nothing here touches a device."""
+runs are dealt to queues, and the queue's host decisions (chsimpy_amd/csrc/chs_batch_host.h) against a model of the seat kernel.
+Nothing here touches a device."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -34,6 +36,21 @@ def test_the_queued_prototypes_are_declared_and_bound():
     assert {'chs_batch_step_n_queued', 'chs_batch_member_rows'} <= declared
     assert {'chs_batch_step_n_queued', 'chs_batch_member_rows'} <= set(_lib.SYMBOLS)
     assert callable(getattr(_lib.Batch, 'step_n_queued'))
+
+
+def test_host_decisions_against_a_model_of_the_seat_kernel(tmp_path):
+    """tests/batch_queue_model.cpp: the step bound and the last-step bookkeeping of chs_batch_step_n_queued, driven
+    step by step with polls two batches late -- every member gets its last-step pair on its last step, nobody is left
+    with steps to do, the bound is the finishing step.  Host C++ only, compiled with the build's compiler."""
+    from chsimpy_amd import _build
+    exe = str(tmp_path / 'batch_queue_model')
+    subprocess.run([os.environ.get('HIPCC', 'hipcc'), '-x', 'c++', '-std=c++17', '-O1', '-Wall', '-I' + _build.CSRC,
+                    os.path.join(ROOT, 'tests', 'batch_queue_model.cpp'), '-o', exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and ' 0 failures' in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    # the header is host code: nothing of HIP in it
+    hdr = open(os.path.join(_build.CSRC, 'chs_batch_host.h')).read()
+    assert not re.search(r'#include\s*[<"](hip/|chs_common|chs_fast)', hdr)
 
 
 @pytest.mark.parametrize('seats', [0, -1, 1.5, True])

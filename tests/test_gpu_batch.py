@@ -231,6 +231,45 @@ def test_zero_step_member_sits_out(gpu):
     assert_same(got[2], ref[1][1], 'member 2')
 
 
+def test_small_poll_batches_with_stops_and_ragged_calls(gpu, monkeypatch):
+    """The plain, fixed-step batch through its polls: N=128 fp64, B=4, time limits that stop member 0 at about step 20
+    and would stop member 2 at about step 33, two calls of per-member lengths [40, 12, 0, 25] and [10, 10, 5, 0], once
+    with CHS_BATCH_STEPS=3 (a poll behind every third step, rows copied out as they complete) and once without (no
+    poll at all).  The two runs are equal in every bit, the E columns included, and both are their single handles.
+    A member with a zero-step call sits it out (test_zero_step_member_sits_out): member 2 takes no step in the first
+    call, so its limit cannot have stopped it by then and its stop reason there is 'None'; member 0, past its limit,
+    is stopped in front of the first step of its second call."""
+    ps = members(128, 4, 400)
+    step_s = ps[0].delt / ps[0].M_tilde
+    for m, k in ((0, 20.5), (2, 33.5)):
+        ps[m].time_max = k * step_s / 60.0
+    calls = ([40, 12, 0, 25], [10, 10, 5, 0])
+    monkeypatch.setenv('CHS_BATCH_STEPS', '3')
+    small = batch_runs(ps, calls)
+    monkeypatch.delenv('CHS_BATCH_STEPS')
+    whole = batch_runs(ps, calls)
+    for m in range(4):
+        for c in range(2):
+            a, b = small[m][c], whole[m][c]
+            assert np.array_equal(a['rows'], b['rows']) and np.array_equal(a['U'], b['U']), (m, c)
+            assert a['state'] == b['state'] and a['counters'] == b['counters'], (m, c)
+    # the single handles make the calls in which their member takes steps
+    ref = [single_runs([ps[m]], [n for n in (calls[0][m], calls[1][m]) if n > 0])[0] for m in range(4)]
+    for got in (small, whole):
+        for m in (0, 1):
+            for c in range(2):
+                assert_same(got[m][c], ref[m][c], f"member {m} call {c}")
+        assert_same(got[2][1], ref[2][0], 'member 2 call 1')
+        assert_same(got[3][0], ref[3][0], 'member 3 call 0')
+        # the call a member sits out leaves it as it was: member 2 as prepared, member 3 as its first call left it
+        assert got[2][0]['rows'].shape == (1, 9)
+        a, b = got[3][1], got[3][0]
+        assert np.array_equal(a['rows'], b['rows']) and np.array_equal(a['U'], b['U'])
+        assert a['state'] == b['state'] and a['counters'] == b['counters']
+        assert [got[m][0]['counters'][3] for m in range(4)] == ['time-limit', 'None', 'None', 'None']
+        assert 15 <= got[0][0]['rows'].shape[0] <= 25
+
+
 def test_run_ensemble_batch_equals_member_path(gpu, tmp_path):
     """run_ensemble(batch=4) against run_ensemble(concurrent=1): 8 runs at N=256, energy stop, post-processing on."""
     p = make(256, 3000, 'fast', full_sim=False)
