@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libchs_hip.so')
 
 CHS_OK, CHS_EINVAL, CHS_EHIP, CHS_ENAN, CHS_ESTATE = 0, -1, -2, -3, -4
 CHS_F64, CHS_F32 = 0, 1
-CHS_ENGINE_AUTO, CHS_ENGINE_DIRECT, CHS_ENGINE_FAST = 0, 1, 2
+CHS_ENGINE_AUTO, CHS_ENGINE_DIRECT, CHS_ENGINE_FAST, CHS_ENGINE_CHIRP = 0, 1, 2, 3
+CHS_CHIRP_AUTO_MIN_N = 129    # the smallest N that 'auto' gives to the chirp engine (include/chs_hip.h)
 CHS_STOP_NONE, CHS_STOP_ENERGY, CHS_STOP_TIME_LIMIT = 0, 1, 2
 CHS_STEP_CARRY_HAT = 1
 CHS_STEP_REDERIVE_HAT = 2
@@ -23,7 +24,7 @@ CHS_NKERNELS = 8
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
-ENGINES = {'auto': CHS_ENGINE_AUTO, 'direct': CHS_ENGINE_DIRECT, 'fast': CHS_ENGINE_FAST}
+ENGINES = {'auto': CHS_ENGINE_AUTO, 'direct': CHS_ENGINE_DIRECT, 'fast': CHS_ENGINE_FAST, 'chirp': CHS_ENGINE_CHIRP}
 DTYPES = {'float64': CHS_F64, 'f64': CHS_F64, 'float32': CHS_F32, 'f32': CHS_F32}
 
 # every symbol include/chs_hip.h declares
@@ -293,7 +294,7 @@ class Engine:
 
     @property
     def engine(self):
-        return {CHS_ENGINE_DIRECT: 'direct', CHS_ENGINE_FAST: 'fast'}[self.lib.chs_engine(self._h)]
+        return {CHS_ENGINE_DIRECT: 'direct', CHS_ENGINE_FAST: 'fast', CHS_ENGINE_CHIRP: 'chirp'}[self.lib.chs_engine(self._h)]
 
     def kernel_names(self):
         out = []

@@ -82,6 +82,7 @@ static void free_engine(Engine* E) {
   if (!E) return;
   hipSetDevice(E->hc.device);
   if (E->engine == CHS_ENGINE_DIRECT) chs_direct_free(E);
+  if (E->engine == CHS_ENGINE_CHIRP) chs_chirp_free(E);
   if (E->engine == CHS_ENGINE_FAST) chs_fast_free(E);
   chs_pointwise_free(E);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
@@ -143,6 +144,11 @@ static void read_env_hooks(Engine* E) {
 #define CHS_POOL_MAX 4
 #define CHS_POOL_FIELD_BYTES ((size_t)160 << 20)
 #define CHS_POOL_TOTAL_BYTES ((size_t)3 << 30)  // device memory the parked engines may hold together
+// CHS_ENGINE_AUTO: the fast engine where it exists, else chirp from CHS_CHIRP_AUTO_MIN_N up to its largest N, else direct
+static int resolve_auto(int N, int dtype) {
+  if (chs_fast_supported(N, dtype)) return CHS_ENGINE_FAST;
+  return (N >= CHS_CHIRP_AUTO_MIN_N && chs_chirp_supported(N)) ? CHS_ENGINE_CHIRP : CHS_ENGINE_DIRECT;
+}
 namespace {
 std::mutex g_pool_mu;
 std::vector<Engine*> g_pool;
@@ -197,7 +203,7 @@ extern "C" int chs_create(const chs_consts* c, const double* lambda, chs_handle*
   CHS_HIP(hipSetDevice(c->device));
   if (pool_enabled()) {
     int want = c->engine;
-    if (want == CHS_ENGINE_AUTO) want = chs_fast_supported(c->N, c->dtype) ? CHS_ENGINE_FAST : CHS_ENGINE_DIRECT;
+    if (want == CHS_ENGINE_AUTO) want = resolve_auto(c->N, c->dtype);
     Engine* P = nullptr;
     {
       std::lock_guard<std::mutex> lock(g_pool_mu);
@@ -226,13 +232,18 @@ extern "C" int chs_create(const chs_consts* c, const double* lambda, chs_handle*
   E->esz = (c->dtype == CHS_F64) ? 8 : 4;
   const int N = c->N;
   int eng = c->engine;
-  if (eng == CHS_ENGINE_AUTO) eng = chs_fast_supported(N, c->dtype) ? CHS_ENGINE_FAST : CHS_ENGINE_DIRECT;
+  if (eng == CHS_ENGINE_AUTO) eng = resolve_auto(N, c->dtype);
   if (eng == CHS_ENGINE_FAST && !chs_fast_supported(N, c->dtype)) {
     delete E;
     chs_set_error("chs_create: the fast engine needs N = 2^k in [128, 8192]");
     return CHS_EINVAL;
   }
-  if (eng != CHS_ENGINE_FAST && eng != CHS_ENGINE_DIRECT) { delete E; chs_set_error("bad engine"); return CHS_EINVAL; }
+  if (eng == CHS_ENGINE_CHIRP && !chs_chirp_supported(N)) {
+    delete E;
+    chs_set_error("chs_create: the chirp engine needs N in [8, 4096]");
+    return CHS_EINVAL;
+  }
+  if (eng != CHS_ENGINE_FAST && eng != CHS_ENGINE_DIRECT && eng != CHS_ENGINE_CHIRP) { delete E; chs_set_error("bad engine"); return CHS_EINVAL; }
   E->engine = eng;
   fill_consts(E, c);
   DevConsts& d = E->dc;
@@ -263,7 +274,9 @@ extern "C" int chs_create(const chs_consts* c, const double* lambda, chs_handle*
   if ((rc = ensure_rows(E))) return fail(rc);
   read_env_hooks(E);
   if ((rc = chs_pointwise_alloc(E))) return fail(rc);
-  if (eng == CHS_ENGINE_DIRECT) rc = chs_direct_init(E); else rc = chs_fast_init(E);
+  if (eng == CHS_ENGINE_DIRECT) rc = chs_direct_init(E);
+  else if (eng == CHS_ENGINE_CHIRP) rc = chs_chirp_init(E);
+  else rc = chs_fast_init(E);
   if (rc) return fail(rc);
 #undef TRY_HIP
   *out = (chs_handle)E;
@@ -446,7 +459,7 @@ extern "C" int chs_prepare(chs_handle h, double row0[9]) {
 
 // hat_U <- dctn(U), solver.py:159
 static int enter(Engine* E) {
-  if (E->engine == CHS_ENGINE_DIRECT) return chs_direct_dct2d(E, E->dU, E->dHat, E->dT1, false);
+  if (chs_natural_engine(E)) return chs_natural_dct2d(E, E->dU, E->dHat, E->dT1, false);
   return chs_fast_enter(E);
 }
 
@@ -458,16 +471,16 @@ static int one_step(Engine* E, bool first, bool last) {
     // fused pipeline: k_col, k_row_inv (+ record partials + next step's row pass), k_step_tail
     return chs_fast_step(E, first, last);
   }
-  if (E->engine == CHS_ENGINE_DIRECT) {
+  if (chs_natural_engine(E)) {
     if ((rc = chs_launch_mu(E))) return rc;        // 166-175
     if ((rc = chs_launch_pre(E))) return rc;       // 177-199, 225
     chs_slot_begin(E, SLOT_FWD);
-    rc = chs_direct_dct2d(E, E->dMU, E->dT2, E->dT1, false);  // dctn(EnergieEut), 201
+    rc = chs_natural_dct2d(E, E->dMU, E->dT2, E->dT1, false);  // dctn(EnergieEut), 201
     chs_slot_end(E, SLOT_FWD);
     if (rc) return rc;
     if ((rc = chs_launch_spectral(E, E->dT2))) return rc;      // 201-206
     chs_slot_begin(E, SLOT_INV);
-    rc = chs_direct_dct2d(E, E->dHat, E->dU, E->dT1, true);   // 208
+    rc = chs_natural_dct2d(E, E->dHat, E->dU, E->dT1, true);   // 208
     chs_slot_end(E, SLOT_INV);
     if (rc) return rc;
   } else {
@@ -693,6 +706,9 @@ extern "C" const char* chs_kernel_name(chs_handle h, int slot) {
                                              "k_diag", "k_fin", "misc"};
   static const char* fast[CHS_NKERNELS] = {"k_row_fwd (prologue)", "k_pre", nullptr, "k_col", "k_row_inv (fused)",
                                            "k_diag", "k_step_tail", "misc"};
+  static const char* chirp[CHS_NKERNELS] = {"k_mu", "k_pre", "k_chirp_lines x2 + k_chirp_transpose x2 (dctn)", "k_spectral",
+                                            "k_chirp_lines x2 + k_chirp_transpose x2 (idctn)", "k_diag", "k_fin", "misc"};
+  if (E->engine == CHS_ENGINE_CHIRP) return chirp[slot];
   return E->engine == CHS_ENGINE_DIRECT ? direct[slot] : fast[slot];
 }
 
@@ -754,7 +770,7 @@ extern "C" int chs_dctn(chs_handle h, const double* host_in, double* host_out, i
   const int halt = s.halt;
   s.halt = 0;
   CHS_HIP(hipMemcpy(E->dState, &s, sizeof s, hipMemcpyHostToDevice));
-  if (E->engine == CHS_ENGINE_DIRECT) rc = chs_direct_dct2d(E, E->dMU, E->dT2, E->dT1, inverse != 0);
+  if (chs_natural_engine(E)) rc = chs_natural_dct2d(E, E->dMU, E->dT2, E->dT1, inverse != 0);
   else rc = chs_fast_dct2d(E, E->dMU, E->dT2, inverse != 0);
   if (rc) return rc;
   rc = download(E, host_out, E->dT2);

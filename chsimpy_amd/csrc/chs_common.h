@@ -250,6 +250,7 @@ struct Engine {
   double* dLambda = nullptr;   // lam_i, N doubles
   void* dD = nullptr;          // direct engine: orthonormal DCT-II matrix D[k][n]
   void* dTw = nullptr;         // fast engine: twiddle tables
+  void* chirp = nullptr;       // chirp engine: its plan and tables (chs_chirp.hip)
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -355,6 +356,19 @@ void chs_pointwise_free(Engine* E);
 int chs_direct_init(Engine* E);
 void chs_direct_free(Engine* E);
 int chs_direct_dct2d(Engine* E, const void* in, void* out, void* tmp, bool inverse);
+
+// ---- chirp engine (chs_chirp.hip) -------------------------------------------
+bool chs_chirp_supported(int N);
+int chs_chirp_init(Engine* E);
+void chs_chirp_free(Engine* E);
+int chs_chirp_dct2d(Engine* E, const void* in, void* out, void* tmp, bool inverse);
+
+// The direct and the chirp engine are one family: natural order in every array, the unfused step of chs_api.hip
+// (one_step); they differ in dct2d alone.
+inline bool chs_natural_engine(const Engine* E) { return E->engine == CHS_ENGINE_DIRECT || E->engine == CHS_ENGINE_CHIRP; }
+inline int chs_natural_dct2d(Engine* E, const void* in, void* out, void* tmp, bool inverse) {
+  return E->engine == CHS_ENGINE_CHIRP ? chs_chirp_dct2d(E, in, out, tmp, inverse) : chs_direct_dct2d(E, in, out, tmp, inverse);
+}
 
 // ---- fast engine (chs_fast.hip) ---------------------------------------------
 bool chs_fast_supported(int N, int dtype);

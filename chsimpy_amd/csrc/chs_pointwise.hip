@@ -719,7 +719,7 @@ int chs_launch_colmin_rows_batch(hipStream_t s, const BatchMember* mem, int B, i
 
 int chs_launch_pre(Engine* E) {
   chs_slot_begin(E, SLOT_PRE);
-  if (E->dc.adaptive_time && E->engine == CHS_ENGINE_DIRECT) {
+  if (E->dc.adaptive_time && chs_natural_engine(E)) {
     const int rcm = launch_colmin(E, E->dPartCol, false, E->nBands, 0);
     if (rcm) { chs_slot_end(E, SLOT_PRE); return rcm; }
   }

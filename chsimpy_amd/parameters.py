@@ -44,7 +44,7 @@ class Parameters:
         # -- engine knobs (not in the reference) --------------------------------
         self.device = 0                 # HIP device ordinal
         self.dtype = 'float64'          # 'float64' | 'float32'
-        self.engine = 'auto'            # 'auto' | 'direct' | 'fast'
+        self.engine = 'auto'            # 'auto' | 'direct' | 'fast' | 'chirp'
 
     def deepcopy(self):
         return copy.deepcopy(self)

@@ -42,9 +42,17 @@ extern "C" {
 #define CHS_F32 1
 
 /* transform engine */
-#define CHS_ENGINE_AUTO 0   /* fast for N = power of two >= 128, else direct     */
+#define CHS_ENGINE_AUTO 0   /* fast for N = 2^k in [128, 8192]; else chirp for
+                               CHS_CHIRP_AUTO_MIN_N <= N <= 4096; else direct    */
 #define CHS_ENGINE_DIRECT 1 /* dense cosine-matrix products, any N >= 8          */
 #define CHS_ENGINE_FAST 2   /* LDS-staged FFT-based row/column DCT passes        */
+#define CHS_ENGINE_CHIRP 3  /* chirp-z (Bluestein) line transforms on power-of-two
+                               FFTs in LDS, any N in [8, 4096]                   */
+/* The smallest N that CHS_ENGINE_AUTO gives to the chirp engine: max(129, N*) with N* the smallest probed N from which
+ * the chirp engine measures at least 1.1x the direct engine's steps per second at every larger probe
+ * (tools/chirp_bench.py, profiles/r08_chirp.txt).  Measured N* = 100 (1.6x there, 2.0x at 129,
+ * 5.8x at 1000, 10.7x at 4000); the floor of 129 keeps the small grids, N = 64 and N = 100, on the direct engine. */
+#define CHS_CHIRP_AUTO_MIN_N 129
 
 /* stop reasons (chsimpy/solver.py:133,198,246) */
 #define CHS_STOP_NONE 0
@@ -211,7 +219,7 @@ int chs_get_mu(chs_handle h, double* host_mu);
  *         4: log(a) for a > 0 (division-based variant)
  *         5: log(a) for a > 0, table-driven (the variant the fused row kernel uses) */
 int chs_test_math(int device, int which, const double* a, const double* b, double* out, int64_t n);
-/* Which engine the handle resolved to (CHS_ENGINE_DIRECT / CHS_ENGINE_FAST). */
+/* Which engine the handle resolved to (CHS_ENGINE_DIRECT / CHS_ENGINE_FAST / CHS_ENGINE_CHIRP). */
 int chs_engine(chs_handle h);
 
 /* Measurement hooks used by bench.py. */

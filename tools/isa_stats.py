@@ -51,7 +51,7 @@ def main():
         cl = re.search(r'; codeLenInByte = (\d+)', body)
         occ = re.search(r'; Occupancy: (\d+)', body)
         short = re.sub(r'FCfg<([^>]*)>', lambda m: 'FCfg<' + m.group(1).replace(' ', '') + '>', d)
-        short = short.split('(')[0][-110:]
+        short = short.replace('(anonymous namespace)::', '').split('(')[0][-110:]
         print(f"{short}\n    code {cl.group(1) if cl else '?':>7} B  vgpr {vg.group(1) if vg else '?':>3}  scratch {sc.group(1) if sc else '?':>4}  occ {occ.group(1) if occ else '?'}"
               f"  | insts {n:6d}  valu {valu:6d} (pk {pk}, f64 {f64}, mov {mov})  lds {lds:4d}  vmem {vmem:4d}  salu {salu:5d} (wait {wait}, barrier {bar})")
 
