@@ -35,11 +35,14 @@ SYMBOLS = (
     'chs_last_error', 'chs_version',
     'chs_batch_create', 'chs_batch_destroy', 'chs_batch_set_U', 'chs_batch_init_U_pcg64', 'chs_batch_get_U',
     'chs_batch_prepare', 'chs_batch_step_n', 'chs_batch_get_state', 'chs_batch_set_state',
-    'chs_batch_step_n_queued', 'chs_batch_member_rows',
+    'chs_batch_step_n_queued', 'chs_batch_member_rows', 'chs_batch_engine',
 )
 
-# the N a batch takes (include/chs_hip.h: chs_batch_create)
+# the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
+# at every other N in [BATCH_CHIRP_MIN_N, BATCH_CHIRP_MAX_N] (CHS_BATCH_CHIRP_MIN_N / _MAX_N) where the members run it
 BATCH_SIZES = (128, 256, 512, 1024, 2048)
+BATCH_CHIRP_MIN_N, BATCH_CHIRP_MAX_N = 8, 4096
+FAST_SIZES = (128, 256, 512, 1024, 2048, 4096, 8192)   # the fast engine's N ('auto' resolves to it there)
 
 
 class chs_consts(C.Structure):
@@ -138,6 +141,7 @@ def load():
     vp, u64p, i64p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
     lib.chs_batch_create.argtypes = [C.POINTER(chs_consts), C.c_int32, dp, C.POINTER(C.c_void_p)]
     lib.chs_batch_destroy.argtypes = [vp]
+    lib.chs_batch_engine.argtypes = [vp]
     lib.chs_batch_set_U.argtypes = [vp, C.c_int32, dp]
     lib.chs_batch_init_U_pcg64.argtypes = [vp, C.c_int32, C.c_double, C.c_double, u64p, u64p]
     lib.chs_batch_get_U.argtypes = [vp, C.c_int32, dp]
@@ -344,6 +348,11 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+    @property
+    def engine(self):
+        """The engine the batch's members run on the device, 'fast' or 'chirp' (chs_batch_engine)."""
+        return {CHS_ENGINE_FAST: 'fast', CHS_ENGINE_CHIRP: 'chirp'}[self.lib.chs_batch_engine(self._h)]
 
     def set_U(self, member, U):
         U = _as_f64(U, (self.N, self.N))

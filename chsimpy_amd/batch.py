@@ -7,9 +7,17 @@ members (``chs_batch_*`` of ``include/chs_hip.h``), so that the members' chains 
 Member by member a ``BatchSolver`` is a ``Solver`` with ``rederive_hat=True``: same constants, start field, records,
 stop rules and quirks (the first ``solve_or_resume`` after ``prepare`` runs ``nsteps-1`` iterations; ``prepare`` does
 not reset ``delt`` / ``time_delta_sum`` / ``skip_check``), every call a literal ``solve_or_resume`` of the reference.
-Its scope: the fast engine, N in {128, 256, 512, 1024, 2048}, one dtype and device for all members, no jitter, and
-``adaptive_time`` set in all members or in none (an adaptive batch: every member adapts its step by its own rule,
-step counter and ``delt_max``); anything else raises ``ValueError`` before the device is touched.
+A batch runs the engine a single ``Solver`` of its members would run.  Its scope: one N, dtype and device for all
+members, no jitter, and
+
+- the fast engine at N in {128, 256, 512, 1024, 2048} (``engine`` 'auto' or 'fast'): ``adaptive_time`` set in all
+  members or in none (an adaptive batch: every member adapts its step by its own rule, step counter and ``delt_max``);
+- the chirp engine at every other N in [8, 4096], where ``engine='chirp'`` asks for it or 'auto' resolves to it
+  (N >= 129 and not a power of two): one launch set of the chirp step's 13 kernels for all members, bit for bit the
+  members' single chirp ``Solver``s.  Fixed time step only, and no seat queue.
+
+Anything else -- the direct engine, 'auto' below N=129, ``engine='chirp'`` at one of the fast engine's five sizes, an
+adaptive chirp batch, ``seats`` with chirp members -- raises ``ValueError`` before the device is touched.
 
     bs = BatchSolver([params_0, params_1, ...])
     bs.prepare()
@@ -28,13 +36,40 @@ from . import _lib
 from .solver import Solver
 
 
-def scope_error(params):
-    """Why one member's parameters are outside what a batch runs (a string), or None."""
+def _auto_is_chirp(N):
+    """Does engine='auto' resolve to the chirp engine at this N (chs_api.hip: resolve_auto)?"""
+    fast = N in _lib.FAST_SIZES
+    return not fast and _lib.CHS_CHIRP_AUTO_MIN_N <= N <= _lib.BATCH_CHIRP_MAX_N
+
+
+def batch_engine(params):
+    """The engine a batch of such members runs, 'fast' or 'chirp' (the rule of chs_batch_create), or None."""
+    N, engine = int(params.N), str(getattr(params, 'engine', 'auto'))
+    if N in _lib.BATCH_SIZES:
+        return 'fast' if engine in ('auto', 'fast') else None
+    if _lib.BATCH_CHIRP_MIN_N <= N <= _lib.BATCH_CHIRP_MAX_N and (engine == 'chirp' or (engine == 'auto' and _auto_is_chirp(N))):
+        return 'chirp'
+    return None
+
+
+def scope_error(params, seats=None):
+    """Why one member's parameters are outside what a batch runs (a string), or None.  ``seats``: the seats of a
+    queue (None: a plain batch)."""
     N = int(params.N)
-    if N not in _lib.BATCH_SIZES:
-        return f"N={N}: a batch takes N in {{{', '.join(str(n) for n in _lib.BATCH_SIZES)}}}"
-    if str(getattr(params, 'engine', 'auto')) not in ('auto', 'fast'):
-        return f"engine={params.engine!r}: a batch runs the fast engine only"
+    engine = str(getattr(params, 'engine', 'auto'))
+    if engine == 'direct':
+        return f"engine={engine!r}: a batch runs the fast engine or the chirp engine"
+    which = batch_engine(params)
+    if which is None:
+        if N in _lib.BATCH_SIZES:
+            return f"engine={engine!r} at N={N}: a batch of the fast engine only"
+        return (f"N={N}: a batch takes N in {{{', '.join(str(n) for n in _lib.BATCH_SIZES)}}} (fast engine), or the chirp "
+                f"engine's N in [{_lib.BATCH_CHIRP_MIN_N}, {_lib.BATCH_CHIRP_MAX_N}] (engine='chirp', or 'auto' from "
+                f"N={_lib.CHS_CHIRP_AUTO_MIN_N} where it is no power of two)")
+    if which == 'chirp' and params.adaptive_time:
+        return "adaptive_time: a chirp batch has no adaptive time step"
+    if which == 'chirp' and seats is not None:
+        return "seats: a chirp batch has no seat queue"
     if str(getattr(params, 'dtype', 'float64')) not in _lib.DTYPES:
         return f"dtype={params.dtype!r} is not supported"
     if params.jitter is not None and 0.0 < params.jitter < 0.1:
@@ -54,7 +89,7 @@ def validate(params_list, seats=None):
     if seats is not None and (isinstance(seats, bool) or int(seats) != seats or int(seats) < 1):
         raise ValueError(f"seats={seats!r}: a queue needs seats >= 1")
     for i, p in enumerate(params_list):
-        why = scope_error(p)
+        why = scope_error(p, seats)
         if why:
             raise ValueError(f"member {i}: {why}")
     a0 = bool(params_list[0].adaptive_time)

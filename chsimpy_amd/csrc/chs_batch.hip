@@ -1,5 +1,7 @@
 // chs_batch.hip -- the batch of include/chs_hip.h: B ensemble members of one N, element type and device advance
-// through the fast engine's step loop together, every step kernel launched ONCE for all of them.
+// through their engine's step loop together, every step kernel launched ONCE for all of them.  A batch runs the engine
+// a single handle of its members would run: the fast engine at N in {128 .. 2048} (everything below up to "A chirp
+// batch"), the chirp engine at every other N it supports (the last paragraph).
 //
 // A member is an ordinary engine (chs_create: its own constants, state, field, transform scratch, partial sums and
 // rows ring); the batch gives all of them one stream and keeps a device array of member records (BatchMember,
@@ -35,13 +37,31 @@
 // device -- the queue's step bound, its last-step bookkeeping, the plain batch's batch_rule_fires -- are in
 // chs_batch_host.h, where a CPU test drives them.  The issue loops stay two: the plain batch knows who runs which step
 // and leaves launches out, the queue does not and issues everything, so one loop would change what one of them launches.
+//
+// A chirp batch (Batch::chirp; N outside the fast batch's set, engine chirp or 'auto' where it resolves to chirp): the
+// members are chirp engines, their records NatMember (chs_nat_batch.h) in Batch::dNat, and a step is the natural
+// engines' unfused sequence of chs_api.hip (one_step) with every launch covering all members --
+//   k_mu, k_pre, dct2d (k_chirp_lines, k_chirp_transpose, twice), k_spectral, dct2d, k_diag, k_fin: 13 launches --
+// through the batched instantiations of the single handle's kernels (chs_pointwise.hip, chs_chirp_batch.hip).  A
+// workgroup leaves at once when its member has halted or has no step left in the call; only k_fin advances the step
+// counter, so the thirteen agree.  call_enter, call_poll, call_take_rows and call_finish are shared with the fast
+// batch: the entry is every member's k_call_begin, the records, then hat_U = dctn(U) of all running members in four
+// launches.  U is stored every step and a time-limit stop in k_pre leaves the previous U in place, as the reference
+// does: there is no rebuild of U after a stop.  Outside a chirp batch's scope: the adaptive step (the natural path
+// reduces partCol in chs_launch_pre, member by member; the batched reduction kernels are BatchMember's), the seat
+// queue, jitter.
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "chs_batch_host.h"
+#include "chs_chirp_host.h"
 #include "chs_fast_kernels.h"
+#include "chs_nat_batch.h"
+
+static_assert(CHS_BATCH_CHIRP_MIN_N == CHS_CHIRP_MIN_N && CHS_BATCH_CHIRP_MAX_N == CHS_CHIRP_MAX_N,
+              "a chirp batch covers every N of the chirp engine (include/chs_hip.h)");
 
 // The batch's per-step bookkeeping: one workgroup per member running the single handle's tail body (chs_tail.h) with
 // the single handle's block size -- THREADS = that of the k_col the tail rides in there (LAST = false: the first step's
@@ -127,6 +147,9 @@ struct Batch {
   hipStream_t stream = nullptr;
   BatchMember* dMem = nullptr;
   std::vector<BatchMember> hMem;
+  bool chirp = false;            // a batch of chirp engines: the records are NatMember, the step the natural sequence
+  NatMember* dNat = nullptr;
+  std::vector<NatMember> hNat;
   DevState* hPoll = nullptr;     // pinned [5][B]: slot 0 = the end of a call, 1..4 = the polls behind the step batches
   hipEvent_t evPoll[4] = {nullptr, nullptr, nullptr, nullptr};
   // the seat queue (chs_batch_step_n_queued; allocated at its first call)
@@ -153,6 +176,7 @@ void batch_free(Batch* b) {
     chs_destroy((chs_handle)b->m[i]);
   }
   if (b->dMem) hipFree(b->dMem);
+  if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
   if (b->dQueue) hipFree(b->dQueue);
   if (b->hQueue) hipHostFree(b->hQueue);
@@ -169,14 +193,33 @@ extern "C" int chs_batch_create(const chs_consts* consts, int32_t B, const doubl
   if (!consts || !lambda || !out) return bad("chs_batch_create: null argument");
   *out = nullptr;
   if (B < 1) return bad("chs_batch_create: B must be >= 1");
+  if (B > CHS_BATCH_MAX_MEMBERS)   // (the member is the grid's y or z dimension: 65535 at the most)
+    return bad("chs_batch_create: B must be <= " + std::to_string(CHS_BATCH_MAX_MEMBERS));
   const chs_consts& c0 = consts[0];
+  // the batch's engine is what a single handle of member 0 would run: the fast engine at the fast batch's sizes, the
+  // chirp engine where it is asked for or where 'auto' resolves to it
+  auto runs_chirp = [](const chs_consts& c) {   // (the engine a member resolves to, not how it is spelled)
+    return c.engine == CHS_ENGINE_CHIRP ||
+           (c.engine == CHS_ENGINE_AUTO && c.N >= CHS_CHIRP_AUTO_MIN_N && !chs_fast_supported(c.N, c.dtype));
+  };
+  const bool chirp = !batch_n_ok(c0.N) && chs_chirp_supported(c0.N) && runs_chirp(c0);
   for (int i = 0; i < B; ++i) {
     const chs_consts& c = consts[i];
     const std::string who = "chs_batch_create: member " + std::to_string(i) + ": ";
     if (c.N != c0.N || c.dtype != c0.dtype || c.device != c0.device)
       return bad(who + "every member needs the N, dtype and device of member 0");
-    if (!batch_n_ok(c.N)) return bad(who + "a batch needs N in {128, 256, 512, 1024, 2048}");
-    if (c.engine == CHS_ENGINE_DIRECT) return bad(who + "a batch runs the fast engine only (engine=direct given)");
+    if (chirp) {
+      if (!runs_chirp(c)) return bad(who + "engine differs from member 0's (a chirp batch: engine chirp, or auto where it resolves to chirp)");
+      if (c.adaptive_time != 0)
+        return bad(who + "adaptive_time: a chirp batch has no adaptive time step (the fast batch has)");
+      continue;
+    }
+    if (c.engine == CHS_ENGINE_DIRECT) return bad(who + "a batch runs the fast or the chirp engine (engine=direct given)");
+    if (batch_n_ok(c.N) && c.engine == CHS_ENGINE_CHIRP)
+      return bad(who + "N=" + std::to_string(c.N) + " is a batch of the fast engine only (engine=chirp given)");
+    if (!batch_n_ok(c.N))
+      return bad(who + "a batch needs N in {128, 256, 512, 1024, 2048} for the fast engine, or the chirp engine (engine=chirp, or "
+                       "auto from N=" + std::to_string(CHS_CHIRP_AUTO_MIN_N) + " where it resolves to chirp) at N in [8, 4096]");
     if (c.engine != CHS_ENGINE_AUTO && c.engine != CHS_ENGINE_FAST) return bad(who + "bad engine");
     if ((c.adaptive_time != 0) != (c0.adaptive_time != 0))
       return bad(who + "adaptive_time differs from member 0's (a batch adapts the step of all its members or of none)");
@@ -187,31 +230,42 @@ extern "C" int chs_batch_create(const chs_consts* consts, int32_t B, const doubl
   auto fail = [&](int rc) { batch_free(b); return rc; };
   for (int i = 0; i < B; ++i) {
     chs_consts c = consts[i];
-    c.engine = CHS_ENGINE_FAST;
+    c.engine = chirp ? CHS_ENGINE_CHIRP : CHS_ENGINE_FAST;
     chs_handle h = nullptr;
     const int rc = chs_create(&c, lambda, &h);
     if (rc) return fail(rc);
     b->m.push_back((Engine*)h);
   }
-  FastPlan* P = (FastPlan*)b->m[0]->dTw;
-  if (!P || !P->col_batch) return fail(bad("chs_batch_create: no batched kernels for this configuration"));
+  b->chirp = chirp;
+  FastPlan* P = chirp ? nullptr : (FastPlan*)b->m[0]->dTw;
+  if (!chirp && (!P || !P->col_batch)) return fail(bad("chs_batch_create: no batched kernels for this configuration"));
 #define TRY_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { chs_hip_fail(e__, #call, __FILE__, __LINE__); return fail(CHS_EHIP); } } while (0)
   TRY_HIP(hipSetDevice(b->device));
   int rc;
-  if ((rc = P->init_batch())) return fail(rc);
+  if ((rc = chirp ? chs_chirp_batch_init(b->m[0]) : P->init_batch())) return fail(rc);
   TRY_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   for (Engine* E : b->m) {   // one stream for all members: their own launches and the batched ones stay in order
     TRY_HIP(hipStreamSynchronize(E->stream));
     b->own.push_back(E->stream);
     E->stream = b->stream;
   }
-  TRY_HIP(hipMalloc(&b->dMem, sizeof(BatchMember) * (size_t)B));
+  if (chirp) TRY_HIP(hipMalloc(&b->dNat, sizeof(NatMember) * (size_t)B));
+  else TRY_HIP(hipMalloc(&b->dMem, sizeof(BatchMember) * (size_t)B));
   TRY_HIP(hipHostMalloc((void**)&b->hPoll, sizeof(DevState) * 5 * (size_t)B, hipHostMallocDefault));
   for (auto& e : b->evPoll) TRY_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 #undef TRY_HIP
-  b->hMem.resize((size_t)B);
+  if (chirp) b->hNat.resize((size_t)B);
+  else b->hMem.resize((size_t)B);
   *out = (chs_batch)b;
   return CHS_OK;
+}
+
+extern "C" int chs_batch_engine(chs_batch h) {
+  Batch* b = as_batch(h);
+  if (!b || b->m.empty()) return CHS_EINVAL;
+  for (const Engine* E : b->m)   // (what the members' handles report, chs_engine: one engine for all of them)
+    if (E->engine != b->m[0]->engine) return CHS_EINVAL;
+  return b->m[0]->engine;
 }
 
 extern "C" int chs_batch_destroy(chs_batch h) {
@@ -316,6 +370,7 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
   const std::string who = c.who;
   if (!b || !c.nsteps || !c.steps_done || !c.status) return bad(who + ": null argument");
   if (flags != 0) return bad(who + ": flags is reserved and must be 0");
+  if (c.queued && b->chirp) return bad(who + ": a chirp batch has no seat queue (chs_batch_step_n runs it)");
   if (c.queued && seats < 1) return bad(who + ": seats must be >= 1");
   const int B = b->B;
   if (c.queued) c.seats = seats < B ? seats : B;
@@ -342,7 +397,29 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
   c.fused &= c.adaptive;
   c.cs0.assign((size_t)B, -1);
   c.copied.assign((size_t)B, 0);
-  for (int i = 0; i < B; ++i) {
+  for (int i = 0; b->chirp && i < B; ++i) {
+    // a chirp member: the re-armed loop and its record; hat_U = dctn(U) follows for all members at once
+    Engine* E = b->m[i];
+    NatMember& r = b->hNat[(size_t)i];
+    std::memset((void*)&r, 0, sizeof r);
+    const int64_t n = c.nsteps[i] > 0 ? c.nsteps[i] : 0;
+    r.nsteps = n;
+    c.steps_done[i] = 0;
+    c.status[i] = CHS_OK;
+    r.st = E->dState;   // (rows_written >= nsteps = 0 keeps the member out of every launch)
+    if (n == 0) continue;
+    if (!E->dRows) return bad(who + ": member " + std::to_string(i) + " has no rows ring");
+    E->stateCached = false; E->resident = false; E->keepResident = false;
+    c.cs0[(size_t)i] = E->csHost;
+    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
+    if ((rc = chs_launch_call_begin(E))) return rc;
+    E->hat_valid = true;
+    r.dc = E->dc;
+    r.arr[NAT_U] = E->dU; r.arr[NAT_MU] = E->dMU; r.arr[NAT_T1] = E->dT1; r.arr[NAT_T2] = E->dT2; r.arr[NAT_HAT] = E->dHat;
+    r.partMu = E->dPartMu; r.partDiag = E->dPartDiag;
+    r.rows = E->dRows; r.rowsCap = E->rowsCap;
+  }
+  for (int i = 0; !b->chirp && i < B; ++i) {
     Engine* E = b->m[i];
     BatchMember& r = b->hMem[(size_t)i];
     std::memset((void*)&r, 0, sizeof r);
@@ -381,6 +458,12 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
   if (const char* bs = getenv("CHS_BATCH_STEPS")) {   // (the test hook of chs_step_n: small batches exercise the polls)
     const long v = atol(bs);
     if (v >= 1 && v <= 8192) c.batch_steps = (int)v;
+  }
+  if (b->chirp) {
+    CHS_HIP(hipMemcpyAsync(b->dNat, b->hNat.data(), sizeof(NatMember) * (size_t)B, hipMemcpyHostToDevice, b->stream));
+    // hat_U = dctn(U) of every running member (solver.py:159), T1 the scratch as in the single handle's entry
+    if (c.running > 0) return chs_chirp_batch_dct2d(b->m[0], b->stream, b->dNat, B, NAT_U, NAT_HAT, NAT_T1, false);
+    return CHS_OK;
   }
   CHS_HIP(hipMemcpyAsync(b->dMem, b->hMem.data(), sizeof(BatchMember) * (size_t)B, hipMemcpyHostToDevice, b->stream));
   return CHS_OK;
@@ -453,7 +536,8 @@ int call_finish(BatchCall& c) {
       return CHS_ESTATE;
     }
     // its row kernel has been keeping U in registers -- the member's own arrays, whoever has its seat by now
-    if (chs_stopped_short(E, s, c.nsteps[i]) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
+    // (a chirp member stores U every step: what it holds after a stop is the field of its last completed step)
+    if (!b->chirp && chs_stopped_short(E, s, c.nsteps[i]) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
     if (s.halt) E->hat_valid = false;
     E->csHost = s.computed_steps;
     const int64_t done = s.rows_written < c.nsteps[i] ? s.rows_written : c.nsteps[i];
@@ -472,6 +556,51 @@ int call_finish(BatchCall& c) {
 }
 }  // namespace
 
+// The issue loop of a chirp batch behind call_enter: the natural step's thirteen launches for all members while some
+// member still has steps in the call; the kernels decide per member who takes part (nat_sits_out).  Polls and the end
+// of the call are the fast batch's.
+static int chirp_step_loop(BatchCall& c) {
+  Batch* b = c.b;
+  const int B = b->B;
+  const int64_t maxn = c.maxn;
+  const int64_t* nsteps = c.nsteps;
+  Engine* E0 = b->m[0];
+  const NatMember* mem = b->dNat;
+  hipStream_t s = b->stream;
+  int rc;
+  int64_t issued = 0;
+  bool stopped = false;
+  while (issued < maxn && !stopped) {
+    int64_t nb = maxn - issued;
+    if (nb > c.batch_steps) nb = c.batch_steps;
+    for (int64_t k = 0; k < nb; ++k) {
+      if ((rc = chs_nat_batch_mu(E0, s, mem, B))) return rc;                                                   // 166-175
+      if ((rc = chs_nat_batch_pre(E0, s, mem, B))) return rc;                                                  // 177-199, 225
+      if ((rc = chs_chirp_batch_dct2d(E0, s, mem, B, NAT_MU, NAT_T2, NAT_T1, false))) return rc;               // 201
+      if ((rc = chs_nat_batch_spectral(E0, s, mem, B))) return rc;                                             // 201-206
+      if ((rc = chs_chirp_batch_dct2d(E0, s, mem, B, NAT_HAT, NAT_U, NAT_T1, true))) return rc;                // 208
+      if ((rc = chs_nat_batch_diag(E0, s, mem, B))) return rc;                                                 // 213-228
+      if ((rc = chs_nat_batch_fin(E0, s, mem, B))) return rc;                                                  // 230-249
+    }
+    issued += nb;
+    if (issued < maxn) {
+      int seen = 0;
+      if ((rc = call_poll(c, [&](int i) { return nsteps[i] > 0; }, [](int) { return (int)CHS_OK; }, &seen))) return rc;
+      if (seen) {
+        const DevState* ps = &b->hPoll[(size_t)seen * B];
+        bool all = true;
+        for (int i = 0; i < B; ++i) {
+          if (nsteps[i] <= 0) continue;
+          if ((rc = call_take_polled(c, i, ps[i]))) return rc;
+          if (!ps[i].halt && nsteps[i] > issued) all = false;   // (as in chs_batch_step_n below)
+        }
+        if (all) stopped = true;
+      }
+    }
+  }
+  return call_finish(c);
+}
+
 // chs_step_n of every member as a literal solve_or_resume call (hat_U = dctn(U) on entry, U stored at the end), the
 // steps of all members issued together.  As in chs_step_n the steps go out in batches, and behind every batch the
 // members' states are fetched; once every member that still has steps to do has halted nothing more is issued.
@@ -482,6 +611,7 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
   int rc;
   if ((rc = call_enter(c, flags, 0))) return rc;
   Batch* b = c.b;
+  if (b->chirp) return chirp_step_loop(c);
   const int B = b->B;
   const int64_t maxn = c.maxn;
   const bool adaptive = c.adaptive, fused = c.fused;

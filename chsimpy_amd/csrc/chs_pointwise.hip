@@ -11,6 +11,7 @@
 #include "chs_common.h"
 #include "chs_math.h"
 #include "chs_tail.h"
+#include "chs_nat_batch.h"
 
 #define PW_THREADS 256
 #define DISPATCH_T(E, expr_d, expr_f) \
@@ -22,13 +23,21 @@
 // k_mu: MU = EnergieEut(U); per-band sum(mu^2); per-band column sums of the
 // adaptive-step integrand (only when `want_col`).
 // grid.x = ceil(N/PW_BAND) row bands, threads sweep the columns.
+// Batch...: empty for the single handle's kernel; one NatSel for a batch of natural-order members (chs_nat_batch.h),
+// the member as the grid's next dimension -- the same for k_pre, k_spectral, k_diag and k_fin below.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, class... Batch>
 __global__ __launch_bounds__(PW_THREADS) void k_mu(const T* __restrict__ U, T* __restrict__ MU, DevConsts dc,
                                                    const DevState* __restrict__ st, double* __restrict__ partMu,
-                                                   double* __restrict__ partCol, int only_col, int cs_offset) {
+                                                   double* __restrict__ partCol, int only_col, int cs_offset, Batch... sel) {
   __shared__ double scratch[32];
-  if (st->halt) return;
+  if constexpr (sizeof...(Batch) != 0) {
+    ConstNatMember& m = nat_member(NatSel{sel...}, blockIdx.y);
+    if (nat_sits_out(m)) return;
+    U = (const T*)m.arr[NAT_U]; MU = (T*)m.arr[NAT_MU]; dc = *(const DevConsts*)&m.dc; st = m.st; partMu = m.partMu;
+  } else {
+    if (st->halt) return;
+  }
   const int N = dc.N;
   const int r0 = blockIdx.x * PW_BAND;
   const int r1 = min(r0 + PW_BAND, N);
@@ -58,12 +67,18 @@ __global__ __launch_bounds__(PW_THREADS) void k_mu(const T* __restrict__ U, T* _
 // k_pre (one block): L2 of the running step, adaptive time step, time
 // bookkeeping and the time-limit stop.
 // ---------------------------------------------------------------------------
-
+template <class... Batch>
 __global__ __launch_bounds__(PW_THREADS) void k_pre(DevConsts dc, DevState* __restrict__ st,
                                                     const double* __restrict__ partMu, int nPartMu,
-                                                    const double* __restrict__ partColMin, int nColMin) {
+                                                    const double* __restrict__ partColMin, int nColMin, Batch... sel) {
   __shared__ double scratch[32];
-  if (st->halt) return;
+  if constexpr (sizeof...(Batch) != 0) {
+    ConstNatMember& m = nat_member(NatSel{sel...}, blockIdx.x);
+    if (nat_sits_out(m)) return;
+    dc = *(const DevConsts*)&m.dc; st = m.st; partMu = m.partMu;
+  } else {
+    if (st->halt) return;
+  }
   double s = 0.0;
   for (int i = threadIdx.x; i < nPartMu; i += PW_THREADS) s += partMu[i];
   const double musq = block_sum(s, scratch);
@@ -101,11 +116,18 @@ int chs_launch_call_begin(Engine* E) {
 // ---------------------------------------------------------------------------
 // k_spectral (direct engine, natural order): hat_U <- (hat_U + Seig*hat_mu)/CHeig
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, class... Batch>
 __global__ __launch_bounds__(PW_THREADS) void k_spectral(T* __restrict__ hatU, const T* __restrict__ hatMu,
                                                          const double* __restrict__ lam, int N,
-                                                         DevState* __restrict__ st) {
-  if (st->halt) return;
+                                                         DevState* __restrict__ st, Batch... sel) {
+  if constexpr (sizeof...(Batch) != 0) {
+    const NatSel b = NatSel{sel...};
+    ConstNatMember& m = nat_member(b, blockIdx.y);
+    if (nat_sits_out(m)) return;
+    hatU = (T*)m.arr[b.dst]; hatMu = (const T*)m.arr[b.src]; st = m.st;
+  } else {
+    if (st->halt) return;
+  }
   const double lam1 = st->lam1, lam2 = st->lam2;
   const size_t total = (size_t)N * N;
   for (size_t idx = (size_t)blockIdx.x * PW_THREADS + threadIdx.x; idx < total;
@@ -148,13 +170,19 @@ __global__ __launch_bounds__(PW_THREADS) void k_sum_fin(const double* __restrict
 // np.gradient(U, delx, axis=[0,1], edge_order=1): interior (f[i+1]-f[i-1])/(2 dx),
 // edges (f[1]-f[0])/dx and (f[N-1]-f[N-2])/dx.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, class... Batch>
 __global__ __launch_bounds__(PW_THREADS) void k_diag(const T* __restrict__ U, DevConsts dc,
                                                      const DevState* __restrict__ st,
-                                                     double* __restrict__ partDiag, int ignore_halt) {
+                                                     double* __restrict__ partDiag, int ignore_halt, Batch... sel) {
   __shared__ double scratch[32];
   __shared__ double2 ltab[CHS_LOGTAB_N];
-  if (!ignore_halt && st->halt) return;
+  if constexpr (sizeof...(Batch) != 0) {
+    ConstNatMember& m = nat_member(NatSel{sel...}, blockIdx.z);
+    if (nat_sits_out(m)) return;
+    U = (const T*)m.arr[NAT_U]; dc = *(const DevConsts*)&m.dc; st = m.st; partDiag = m.partDiag;
+  } else {
+    if (!ignore_halt && st->halt) return;
+  }
   if constexpr (sizeof(T) == 8) {
     for (int t = threadIdx.x; t < CHS_LOGTAB_N; t += PW_THREADS) ltab[t] = reinterpret_cast<const double2*>(chs_log_table)[t];
     __syncthreads();
@@ -218,13 +246,20 @@ __global__ __launch_bounds__(PW_THREADS) void k_diag(const T* __restrict__ U, De
 // Slot 4 carries time_passed; the host applies ** (1/3) (solver.py:230) with
 // the same libm pow the reference's Python float uses.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, class... Batch>
 __global__ __launch_bounds__(PW_THREADS) void k_fin(const T* __restrict__ U, DevConsts dc, DevState* __restrict__ st,
                                                     const double* __restrict__ partDiag, int nPart,
                                                     double* __restrict__ rows, long long rowsCap, int prepare_mode,
-                                                    const double* __restrict__ partE2, int nE2, int fused) {
+                                                    const double* __restrict__ partE2, int nE2, int fused, Batch... sel) {
   __shared__ double scratch[32];
-  if (!prepare_mode && st->halt) return;
+  if constexpr (sizeof...(Batch) != 0) {
+    ConstNatMember& m = nat_member(NatSel{sel...}, blockIdx.x);
+    if (nat_sits_out(m)) return;
+    U = (const T*)m.arr[NAT_U]; dc = *(const DevConsts*)&m.dc; st = m.st; partDiag = m.partDiag;
+    rows = m.rows; rowsCap = m.rowsCap;
+  } else {
+    if (!prepare_mode && st->halt) return;
+  }
   const int N = dc.N;
   double sE = 0.0, sG = 0.0, sP = 0.0, sS = 0.0;
   for (int i = threadIdx.x; i < nPart; i += PW_THREADS) {
@@ -723,7 +758,7 @@ int chs_launch_pre(Engine* E) {
     const int rcm = launch_colmin(E, E->dPartCol, false, E->nBands, 0);
     if (rcm) { chs_slot_end(E, SLOT_PRE); return rcm; }
   }
-  k_pre<<<1, PW_THREADS, 0, E->stream>>>(E->dc, E->dState, E->dPartMu, E->nPartMu, E->dPartColMin,
+  k_pre<><<<1, PW_THREADS, 0, E->stream>>>(E->dc, E->dState, E->dPartMu, E->nPartMu, E->dPartColMin,
                                          E->nColMinBlocks);
   chs_slot_end(E, SLOT_PRE);
   CHS_HIP(hipGetLastError());
@@ -779,6 +814,60 @@ int chs_launch_fin(Engine* E, int prepare_mode, int fused) {
                                                     fused ? E->nRowBlocks : E->nDiagBlocks, E->dRows, E->rowsCap,
                                                     prepare_mode, E->dPartE2, E->nPartE2, fused)));
   chs_slot_end(E, SLOT_FIN);
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The natural step's pointwise kernels for a batch (chs_nat_batch.h): the launches of chs_launch_mu / _pre / _spectral
+// / _diag / _fin above with the member as one grid dimension more.  What a member's record does not carry -- N, the
+// band and block counts, the eigenvalue table -- is member 0's: the same for all members of a batch.  No adaptive
+// step here (chs_batch_create refuses it: the natural path reduces partCol in chs_launch_pre, member by member).
+// ---------------------------------------------------------------------------
+int chs_nat_batch_mu(Engine* E0, hipStream_t s, const NatMember* mem, int B) {
+  const dim3 grid(E0->nBands, B);
+  const NatSel sel{mem, NAT_U, NAT_MU};
+  DISPATCH_T(E0,
+    (k_mu<double, NatSel><<<grid, PW_THREADS, 0, s>>>(nullptr, nullptr, E0->dc, nullptr, nullptr, nullptr, 0, 0, sel)),
+    (k_mu<float, NatSel><<<grid, PW_THREADS, 0, s>>>(nullptr, nullptr, E0->dc, nullptr, nullptr, nullptr, 0, 0, sel)));
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+int chs_nat_batch_pre(Engine* E0, hipStream_t s, const NatMember* mem, int B) {
+  k_pre<NatSel><<<B, PW_THREADS, 0, s>>>(E0->dc, nullptr, nullptr, E0->nPartMu, nullptr, 0, NatSel{mem, 0, 0});
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+int chs_nat_batch_spectral(Engine* E0, hipStream_t s, const NatMember* mem, int B) {
+  const size_t total = (size_t)E0->N * E0->N;
+  int blocks = (int)((total + PW_THREADS - 1) / PW_THREADS);
+  if (blocks > 4096) blocks = 4096;
+  const dim3 grid(blocks, B);
+  const NatSel sel{mem, NAT_T2, NAT_HAT};   // hat_U <- (hat_U + Seig * T2) / CHeig
+  DISPATCH_T(E0,
+    (k_spectral<double, NatSel><<<grid, PW_THREADS, 0, s>>>(nullptr, nullptr, E0->dLambda, E0->N, nullptr, sel)),
+    (k_spectral<float, NatSel><<<grid, PW_THREADS, 0, s>>>(nullptr, nullptr, E0->dLambda, E0->N, nullptr, sel)));
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+int chs_nat_batch_diag(Engine* E0, hipStream_t s, const NatMember* mem, int B) {
+  const dim3 grid((E0->N + DIAG_BAND - 1) / DIAG_BAND, (E0->N + PW_THREADS - 1) / PW_THREADS, B);
+  const NatSel sel{mem, NAT_U, NAT_U};
+  DISPATCH_T(E0,
+    (k_diag<double, NatSel><<<grid, PW_THREADS, 0, s>>>(nullptr, E0->dc, nullptr, nullptr, 0, sel)),
+    (k_diag<float, NatSel><<<grid, PW_THREADS, 0, s>>>(nullptr, E0->dc, nullptr, nullptr, 0, sel)));
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
+int chs_nat_batch_fin(Engine* E0, hipStream_t s, const NatMember* mem, int B) {
+  const NatSel sel{mem, NAT_U, NAT_U};
+  DISPATCH_T(E0,
+    (k_fin<double, NatSel><<<B, PW_THREADS, 0, s>>>(nullptr, E0->dc, nullptr, nullptr, E0->nDiagBlocks, nullptr, 0, 0, nullptr, 0, 0, sel)),
+    (k_fin<float, NatSel><<<B, PW_THREADS, 0, s>>>(nullptr, E0->dc, nullptr, nullptr, E0->nDiagBlocks, nullptr, 0, 0, nullptr, 0, 0, sel)));
   CHS_HIP(hipGetLastError());
   return CHS_OK;
 }

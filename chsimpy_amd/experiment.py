@@ -223,12 +223,13 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
     once for the whole group (``batch_fn(run_ids, init_params, rand_values, A_list)`` -> their 12-tuples; default
     run_batch_gpu).  An ensemble with ``adaptive_time`` is taken too: its members all adapt their step.  A configuration
     outside the batch's scope (chsimpy_amd.batch.scope_error: N, engine, jitter) runs member by member instead, with a
-    note.
+    note.  An N of the chirp engine (engine='chirp', or 'auto' from N=129 where N is no power of two) is a chirp batch.
 
     ``queue`` (with ``batch`` > 0): the rank's members form one seat queue with ``batch`` seats instead of groups of
     ``batch`` -- a member that stops hands its seat to the next one on the device, so the device does not run the tail
     of every group nearly empty.  Every member of a queue owns its device arrays from the start, so the runs are cut
-    into queues of at most ``queue_members``; ``batch_fn`` is called once per queue."""
+    into queues of at most ``queue_members``; ``batch_fn`` is called once per queue.  A chirp batch has no queue:
+    ``queue`` at such an N runs member by member, with the note."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
@@ -236,7 +237,7 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
     ids = my_run_ids(nr_items, rank, world)
     if batch > 0 and batch_fn is None:
         from .batch import scope_error
-        why = scope_error(init_params)
+        why = scope_error(init_params, seats=batch if queue else None)
         if why:
             print(f"chsimpy_amd.experiment: --batch {batch} not taken ({why}); members run one by one")
             batch = 0

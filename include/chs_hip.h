@@ -237,19 +237,33 @@ const char* chs_last_error(void);
 const char* chs_version(void);
 
 /* ---- Batches: B ensemble members advanced together --------------------------------------------------------------
- * A batch holds B members of the same N, dtype and device (the fast engine, N in {128, 256, 512, 1024, 2048}) that
- * either all keep a fixed time step or all adapt it (adaptive_time, solver.py:177-193: each member by its own rule,
- * counter and delt_max); every other scalar of chs_consts -- A0, A1, full_sim, time_limit_s, delt, delt_max,
- * threshold, ... -- is the member's own.  Each step kernel is launched once for all members, so that the short dependent chains of small grids
- * overlap each other on the device.  For every member m the semantics are those of chs_prepare / chs_step_n /
- * chs_get_state on a single handle created from consts[m]; every chs_batch_step_n is a literal solve_or_resume call
- * (hat_U = dctn(U) recomputed on entry, solver.py:159; U stored at the end).  One lambda table for all members.
+ * A batch holds B members of the same N, dtype and device and runs the engine a single handle of its members would run:
+ *   - the fast engine at N in {128, 256, 512, 1024, 2048} (engine = CHS_ENGINE_AUTO or CHS_ENGINE_FAST): its members
+ *     either all keep a fixed time step or all adapt it (adaptive_time, solver.py:177-193: each member by its own rule,
+ *     counter and delt_max);
+ *   - the chirp engine at every other N in [CHS_BATCH_CHIRP_MIN_N, CHS_BATCH_CHIRP_MAX_N] = [8, 4096], where engine =
+ *     CHS_ENGINE_CHIRP asks for it or CHS_ENGINE_AUTO resolves to it (N >= CHS_CHIRP_AUTO_MIN_N, not a power of two):
+ *     fixed time step only, and no seat queue (chs_batch_step_n_queued returns CHS_EINVAL).
+ * Every other scalar of chs_consts -- A0, A1, full_sim, time_limit_s, delt, delt_max, threshold, ... -- is the member's
+ * own.  Each step kernel is launched once for all members, so that the short dependent chains of small grids overlap
+ * each other on the device (the chirp engine's step: 13 launches for the whole batch).  For every member m the semantics
+ * are those of chs_prepare / chs_step_n / chs_get_state on a single handle created from consts[m] with the batch's
+ * engine; every chs_batch_step_n is a literal solve_or_resume call (hat_U = dctn(U) recomputed on entry, solver.py:159;
+ * U stored at the end), and a member of a chirp batch is bit for bit its single chirp handle stepped with
+ * CHS_STEP_REDERIVE_HAT.  One lambda table for all members.
  * chs_batch_create returns CHS_EINVAL (chs_last_error says why) for B < 1, members that differ in N, dtype or device,
- * an N outside the set above, engine = CHS_ENGINE_DIRECT, or a member whose adaptive_time differs from member 0's
- * (the message names the first such member).  Jitter has no batched counterpart.  `member` = -1 addresses every member where noted. */
+ * an N that neither engine's batch takes (engine = CHS_ENGINE_CHIRP at one of the fast batch's five sizes included:
+ * those are batches of the fast engine only), engine = CHS_ENGINE_DIRECT, a member of a fast batch whose adaptive_time
+ * differs from member 0's, or a member of a chirp batch with adaptive_time set (the message names the first such
+ * member).  Jitter has no batched counterpart.  `member` = -1 addresses every member where noted. */
+#define CHS_BATCH_CHIRP_MIN_N 8
+#define CHS_BATCH_CHIRP_MAX_N 4096
+#define CHS_BATCH_MAX_MEMBERS 65535 /* B of chs_batch_create: the member is a grid dimension of every batched launch */
 typedef struct chs_batch_s* chs_batch;
 int chs_batch_create(const chs_consts* consts /*[B]*/, int32_t B, const double* lambda, chs_batch* out);
 int chs_batch_destroy(chs_batch b);
+/* The engine the batch's members run (what chs_engine reports for each of them): CHS_ENGINE_FAST or CHS_ENGINE_CHIRP. */
+int chs_batch_engine(chs_batch b);
 int chs_batch_set_U(chs_batch b, int32_t member, const double* host_U);           /* member -1: all */
 int chs_batch_init_U_pcg64(chs_batch b, int32_t member, double base, double scale,
                            const uint64_t state[2], const uint64_t inc[2]);        /* member -1: all */
@@ -273,7 +287,7 @@ int chs_batch_set_state(chs_batch b, int32_t member, const chs_state* in);
  * would in chs_batch_step_n).  Member by member the call means what chs_batch_step_n means, and its results are bit
  * for bit those of chs_batch_step_n: a literal solve_or_resume call, the same stop rules, NaN handling and rebuild of U
  * after a stop; nsteps[m] = 0 sits the call out.  A batch of R members is a queue of R members: seats >= R behaves
- * like chs_batch_step_n; seats < 1 and flags != 0 return CHS_EINVAL.  The rows are kept by the batch as the polls of
+ * like chs_batch_step_n; seats < 1, flags != 0 and a chirp batch (it has no queue) return CHS_EINVAL.  The rows are kept by the batch as the polls of
  * the call copy them out of the members' rings (no [R][max nsteps][9] array: 72 MB per member at ntmax = 1e6) until
  * the next queued call; chs_batch_member_rows hands over the first n <= steps_done[member] of them. */
 int chs_batch_step_n_queued(chs_batch b, int32_t seats, const int64_t* nsteps /*[R]*/, int32_t flags,

@@ -16,7 +16,17 @@ default experiment (energy stop, ntmax 1e6) of --members M runs at grid size N t
 batch=S)), one plain batch of all M, and one queue of S seats (batch=S, queue=True); 1 warm-up + 3 repetitions each,
 member-steps/s and end-to-end seconds.
 
+--engine chirp: the chirp batch (grid sizes outside the fast engine's set).  Every configuration runs in a process of
+its own (a fresh child per row, one after the other; the first child that fails ends the bench): 200 full_sim steps in
+one literal call, 1 warm-up + 3 repetitions, median and spread (max - min) of the member-steps/s.  fp64 at N in {100,
+200, 500, 1000, 2000} and fp32 at N=500, B in {1, 4, 16, 64} -- B=64 only where the members' arrays (5 of N^2 elements
+each) stay under 4 GiB together.  Baseline of every row: the same B members as single chirp handles stepped one after
+the other, which is what --batch did at these N before there was a chirp batch; and run_ensemble(concurrent=3) per N.
+With --only N,dtype,B (B a number, or `c3` for the concurrent=3 row) it measures that one row in this process.
+
 usage: tools/batch_bench.py [--quick] [--adaptive] [--only N,dtype,B [--once]] [--seats S] [--default N [--members M]]
+                            [--engine chirp [--quick]]
+    --engine chirp --quick: N in {100, 1000} fp64, B in {1, 4, 16}, no concurrent=3 row
     --quick: N=512 fp64 only, B in {1, 16}
     --only:  one batched row and nothing else, e.g. --only 512,float64,16; --once: a single call without warm-up or
              repetitions (what a kernel trace should hold)
@@ -40,9 +50,11 @@ REPS = 3
 ADAPTIVE = False
 
 
-def members(N, B, dtype='float64', ntmax=STEPS + 1, full_sim=True):
+def members(N, B, dtype='float64', ntmax=STEPS + 1, full_sim=True, engine=None):
     init = chsimpy_amd.Parameters()
     init.N, init.ntmax, init.full_sim, init.kappa_tilde, init.dtype = N, ntmax, full_sim, KAPPA, dtype
+    if engine:
+        init.engine = engine
     init.file_id = '/tmp/batch_bench'
     if ADAPTIVE:
         init.adaptive_time, init.delt_max = True, 4.9e-7 / N
@@ -144,8 +156,100 @@ def default_queue(N, M, S):
               f"{sum(steps)} member-steps ({sum(steps) / mean:9.0f}/s), stop steps {min(steps)}..{max(steps)}", flush=True)
 
 
+# ---------------------------------------------------------------------------
+# --engine chirp
+# ---------------------------------------------------------------------------
+CHIRP_STEPS = 200
+CHIRP_ROWS = [(100, 'float64'), (200, 'float64'), (500, 'float64'), (1000, 'float64'), (2000, 'float64'), (500, 'float32')]
+CHIRP_BS = (1, 4, 16, 64)
+CHIRP_BYTES_MAX = 4 << 30
+
+
+def chirp_fits(N, dtype, B):
+    return 5 * N * N * (8 if dtype == 'float64' else 4) * B <= CHIRP_BYTES_MAX
+
+
+def _rates(work, fn):
+    """1 warm-up + REPS repetitions of fn() -> seconds; (median, spread) of work/seconds"""
+    fn()
+    r = sorted(work / fn() for _ in range(REPS))
+    return float(np.median(r)), float(r[-1] - r[0])
+
+
+def chirp_row(N, dtype, B):
+    """One row, in this process: the batch of B chirp members and the same members one by one."""
+    _, _, ps = members(N, B, dtype, ntmax=CHIRP_STEPS + 1, engine='chirp')
+    bs = BatchSolver(ps)
+
+    def run_batch():
+        bs.prepare()
+        t0 = time.perf_counter()
+        bs.solve_or_resume(CHIRP_STEPS + 1)
+        return time.perf_counter() - t0
+    b_med, b_spread = _rates(B * CHIRP_STEPS, run_batch)
+    assert all(s.solution.computed_steps == CHIRP_STEPS + 1 for s in bs.solvers)
+    bs.close(fetch_U=False)
+    singles = [chsimpy_amd.Solver(p) for p in ps]
+    for s in singles:
+        s.rederive_hat = True
+
+    def run_singles():
+        for s in singles:
+            s.prepare()
+        t0 = time.perf_counter()
+        for s in singles:
+            s.solve_or_resume(CHIRP_STEPS + 1)
+        return time.perf_counter() - t0
+    s_med, s_spread = _rates(B * CHIRP_STEPS, run_singles)
+    assert singles[0]._engine.engine == 'chirp'
+    for s in singles:
+        s.close(fetch_U=False)
+    print(f"N={N} {dtype} chirp batch B={B:3d}: {b_med:9.0f} (spread {b_spread:8.0f}) member-steps/s   one by one: "
+          f"{s_med:9.0f} (spread {s_spread:8.0f})   x{b_med / s_med:5.2f}", flush=True)
+
+
+def chirp_c3(N, dtype, runs=6):
+    init, ep, _ = members(N, runs, dtype, ntmax=CHIRP_STEPS + 1, engine='chirp')
+
+    def run():
+        t0 = time.perf_counter()
+        ex.run_ensemble(init, ep, concurrent=3,
+                        run_fn=lambda i, p, rv, al: ex.run_experiment_gpu(i, p, rv, al, None, postprocess=False))
+        return time.perf_counter() - t0
+    med, spread = _rates(runs * CHIRP_STEPS, run)
+    print(f"N={N} {dtype} chirp run_ensemble(concurrent=3, {runs} runs, end to end): {med:9.0f} (spread {spread:8.0f}) "
+          f"member-steps/s", flush=True)
+
+
+def chirp_bench(quick):
+    import subprocess
+    print(f"# chirp batch bench: full_sim, one literal {CHIRP_STEPS}-step call, every row in a process of its own, 1 warm-up "
+          f"+ {REPS} reps; member-steps/s median (spread = max - min)", flush=True)
+    rows = [(100, 'float64'), (1000, 'float64')] if quick else CHIRP_ROWS
+    for N, dt in rows:
+        todo = ([] if quick else ['c3']) + [str(B) for B in ((1, 4, 16) if quick else CHIRP_BS) if chirp_fits(N, dt, B)]
+        for what in todo:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--engine', 'chirp', '--only', f"{N},{dt},{what}"],
+                               timeout=300)
+            if r.returncode != 0:   # nothing more is started on a device behind a failure
+                print(f"N={N} {dt} {what}: the child ended with {r.returncode}; bench stopped", flush=True)
+                sys.exit(1)
+
+
 def main():
     global ADAPTIVE
+    if '--engine' in sys.argv:
+        if sys.argv[sys.argv.index('--engine') + 1] != 'chirp':
+            sys.exit("--engine takes chirp (the fast engine's batch is the default)")
+        if '--only' in sys.argv:
+            N, dt, B = sys.argv[sys.argv.index('--only') + 1].split(',')
+            if B == 'c3':
+                chirp_c3(int(N), dt)
+            else:
+                chirp_row(int(N), dt, int(B))
+        else:
+            chirp_bench('--quick' in sys.argv)
+        return
     quick = '--quick' in sys.argv
     ADAPTIVE = '--adaptive' in sys.argv
     mode = 'adaptive step (delt_max = 4.9e-7/N), ' if ADAPTIVE else ''

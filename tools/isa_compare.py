@@ -18,7 +18,8 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-TUS = ['chs_fast_f64.hip', 'chs_fast_f32.hip', 'chs_batch.hip', 'chs_pointwise.hip', 'chs_direct.hip', 'chs_fast.hip', 'chs_api.hip']
+TUS = ['chs_fast_f64.hip', 'chs_fast_f32.hip', 'chs_batch.hip', 'chs_pointwise.hip', 'chs_direct.hip', 'chs_fast.hip', 'chs_api.hip',
+       'chs_chirp.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-Wno-unused-value', '-Wno-unused-result', '-Wno-pass-failed',
          '-DCHS_TEST_HOOKS=1']
 
