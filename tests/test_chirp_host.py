@@ -27,8 +27,10 @@ def _model():
 cm = _model()
 
 
+# every P = 16 ... 8192, and both ends of the ranges of P = 128, 1024 and 4096 (the plans (2, 1), (3, 1) and (3, 0))
 @pytest.mark.parametrize('N, P', [(8, 16), (9, 32), (24, 64), (100, 256), (127, 256), (129, 512), (1000, 2048),
-                                  (2049, 8192), (4096, 8192)])
+                                  (2049, 8192), (4096, 8192), (40, 128), (64, 128), (65, 256), (301, 1024),
+                                  (512, 1024), (513, 2048), (1025, 4096), (2048, 4096)])
 def test_plan_takes_the_smallest_power_of_two(N, P):
     pl = cm.plan(N)
     assert pl['P'] == P and 1 << pl['logP'] == P
@@ -40,7 +42,7 @@ def test_plan_takes_the_smallest_power_of_two(N, P):
 def test_the_models_pass_view_is_the_kernels_position_map():
     """The passes of the model work on a reshaped view of the line; the kernel computes positions from lane and
     register number.  The two are the same map, and every pass touches every position once."""
-    for N in (8, 9, 24, 100, 129, 1000):
+    for N in (8, 9, 24, 100, 129, 1000, 40, 301, 1025, 2049):
         pl = cm.plan(N)
         P = pl['P']
         lds = np.arange(P)[None, :]
@@ -53,7 +55,7 @@ def test_the_models_pass_view_is_the_kernels_position_map():
                 assert np.array_equal(v[t >> ls, q, t & ((1 << ls) - 1)], pos[:, q])
 
 
-@pytest.mark.parametrize('N', [8, 9, 24, 100, 127, 129, 1000, 2049])
+@pytest.mark.parametrize('N', [8, 9, 24, 100, 127, 129, 1000, 2049, 40, 64, 301, 1025])
 def test_model_matches_scipy_forward_and_inverse(N):
     """The device's dataflow restated in numpy: reorder for odd and even N, padding, the digit-reversed Bhat order with
     the chosen radices, the inverse pairing -- forward and inverse, rows and columns."""
@@ -85,13 +87,25 @@ def test_model_single_basis_modes(N):
 
 
 def test_model_in_complex64_stays_within_the_fp32_tolerance():
-    """Tables rounded once to float, arithmetic in complex64: the fp32 engine's tolerance (4e-6) holds with room."""
+    """Tables rounded once to float, arithmetic in complex64: the fp32 engine's tolerance (4e-6) holds with room at
+    N = 100, and the model stays under the 2e-5 cap of the bound that takes over above N = 1000."""
     N = 100
     tb = cm.tables(N, np.complex64)
     x = np.random.default_rng(1).standard_normal((N, N))
     y = fftpack.dctn(x, norm='ortho')
     assert cm.dct2d(x, tb).dtype == np.float32
     assert np.max(np.abs(cm.dct2d(x, tb) - y)) <= 4e-6 * np.max(np.abs(y))
+    # N = 1025 (P = 4096, three exchange passes): above N = 1000 the bound of the GPU test is twice this model's own
+    # error and never above 2e-5, the project's fp32 transform tolerance (tests/test_gpu_parity.py: test_fp32_dctn).
+    # The model itself has to stay under that cap, in both directions, on the GPU test's input.
+    N = 1025
+    tb = cm.tables(N, np.complex64)
+    x = np.random.default_rng(N).standard_normal((N, N))
+    y = fftpack.dctn(x, norm='ortho')
+    ef = float(np.max(np.abs(cm.dct2d(x, tb) - y)) / np.max(np.abs(y)))
+    ei = float(np.max(np.abs(cm.dct2d(y, tb, inverse=True) - x)) / np.max(np.abs(x)))
+    assert ef <= 2e-5, f"complex64 model N={N}: forward {ef:.3e} of the largest entry"
+    assert ei <= 2e-5, f"complex64 model N={N}: inverse {ei:.3e} of the largest entry"
 
 
 @pytest.fixture(scope='module')
@@ -120,7 +134,7 @@ def test_host_tables_against_direct_evaluation(tables_exe):
     assert re.findall(r'#include\s*"([^"]+)"', prog) == ['chs_chirp_host.h']
 
 
-@pytest.mark.parametrize('N', [9, 100, 129])
+@pytest.mark.parametrize('N', [9, 100, 129, 40, 301])
 def test_model_tables_are_the_headers_tables(tables_exe, N):
     """The plan and every table of chs_chirp_host.h, rounded to double and printed by `chirp_tables --dump N`, against
     the model's own (tools/chirp_model.py).  Both evaluate the chirp, the factors and the twiddles in extended precision

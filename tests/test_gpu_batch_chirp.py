@@ -83,19 +83,24 @@ def assert_same(a, b, what=''):
     assert a['counters'] == b['counters'], (what, a['counters'], b['counters'])
 
 
-# N, B, engine, calls: the smallest shapes at which each path of the line kernel's launch can go wrong
+# N, B, engine, calls, member settings: the smallest shapes at which each path of the line kernel's launch can go wrong
 SHAPES = [
-    (24, 5, 'chirp', (20, 3)),      # P=64: 32 lines per workgroup, one partial workgroup per member
-    (100, 3, 'chirp', (40, 7)),     # P=256: 13 workgroups per member, the last with 4 of 8 lines; N no multiple of the 32-wide tile
-    (129, 2, 'auto', (10,)),        # P=512; 'auto' resolves to chirp
-    (1025, 2, 'chirp', (3,)),       # P=4096: the 512-thread launch of the MAXT = 1024 instantiation
-    (2049, 2, 'chirp', (2,)),       # P=8192: 1024 threads, 132 KiB of LDS
+    (24, 5, 'chirp', (20, 3), {}),      # P=64: 32 lines per workgroup, one partial workgroup per member
+    (100, 3, 'chirp', (40, 7), {}),     # P=256: 13 workgroups per member, the last with 4 of 8 lines; N no multiple of the 32-wide tile
+    (129, 2, 'auto', (10,), {}),        # P=512; 'auto' resolves to chirp
+    (1025, 2, 'chirp', (3,), {}),       # P=4096: the 512-thread launch of the MAXT = 1024 instantiation
+    (2049, 2, 'chirp', (2,), {}),       # P=8192: 1024 threads, 132 KiB of LDS
+    # the batched float launches of 512 and 1024 threads (the single handles they are compared with meet scipy and the
+    # oracle at these sizes in tests/test_gpu_chirp.py and tests/test_gpu_chirp_sizes.py)
+    (1025, 2, 'chirp', (3,), dict(dtype='float32')),
+    (2049, 2, 'chirp', (2,), dict(dtype='float32')),
 ]
 
 
-@pytest.mark.parametrize('N, B, engine, calls', SHAPES, ids=[f"N{s[0]}" for s in SHAPES])
-def test_bitwise_equal_to_single_chirp_handles(gpu, N, B, engine, calls):
-    ps = members(N, B, sum(calls) + 2, engine)
+@pytest.mark.parametrize('N, B, engine, calls, kw', SHAPES,
+                         ids=[f"N{s[0]}" + ''.join(f"-{v}" for v in s[4].values()) for s in SHAPES])
+def test_bitwise_equal_to_single_chirp_handles(gpu, N, B, engine, calls, kw):
+    ps = members(N, B, sum(calls) + 2, engine, **kw)
     engines, of_batch = [], []
     got, ref = batch_runs(ps, calls, engines=of_batch), single_runs(ps, calls, engines=engines)
     # the members of the device batch report the engine a single handle of them runs, and the host rule says the same
@@ -103,7 +108,7 @@ def test_bitwise_equal_to_single_chirp_handles(gpu, N, B, engine, calls):
     assert engines == ['chirp'] * B and batch_engine(ps[0]) == 'chirp', engines
     for m in range(B):
         for c in range(len(calls)):
-            assert_same(got[m][c], ref[m][c], f"N={N} member {m} call {c}")
+            assert_same(got[m][c], ref[m][c], f"N={N} {kw} member {m} call {c}")
         assert got[m][-1]['rows'].shape[0] == 1 + sum(calls) - 1   # (the first call after prepare runs nsteps-1 iterations)
     assert got[0][0]['rows'][-1, 1] != got[1][0]['rows'][-1, 1]   # the members are different runs
 
