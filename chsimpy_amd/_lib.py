@@ -36,6 +36,7 @@ SYMBOLS = (
     'chs_batch_create', 'chs_batch_destroy', 'chs_batch_set_U', 'chs_batch_init_U_pcg64', 'chs_batch_get_U',
     'chs_batch_prepare', 'chs_batch_step_n', 'chs_batch_get_state', 'chs_batch_set_state',
     'chs_batch_step_n_queued', 'chs_batch_member_rows', 'chs_batch_engine',
+    'chs_structure_factor_bins', 'chs_structure_factor', 'chs_structure_factor_last_ms', 'chs_batch_structure_factor',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -151,6 +152,11 @@ def load():
     lib.chs_batch_set_state.argtypes = [vp, C.c_int32, C.POINTER(chs_state)]
     lib.chs_batch_step_n_queued.argtypes = [vp, C.c_int32, i64p, C.c_int32, i64p, C.POINTER(C.c_int32)]
     lib.chs_batch_member_rows.argtypes = [vp, C.c_int32, dp, C.c_int64]
+    lib.chs_structure_factor_bins.argtypes = [C.c_int32]
+    lib.chs_structure_factor_bins.restype = C.c_int32
+    lib.chs_structure_factor.argtypes = [vp, dp, C.c_int32]
+    lib.chs_structure_factor_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_structure_factor.argtypes = [vp, C.c_int32, dp, C.c_int32]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -296,6 +302,19 @@ class Engine:
         self._check(self.lib.chs_get_mu(self._h, _dptr(M)), 'chs_get_mu')
         return M
 
+    def structure_factor(self):
+        """Ssum[nb] of the field the device holds (chs_structure_factor; chsimpy_amd/spectrum.py derives the rest)."""
+        nb = int(self.lib.chs_structure_factor_bins(self.N))
+        ssum = np.empty(nb, dtype=np.float64)
+        self._check(self.lib.chs_structure_factor(self._h, _dptr(ssum), nb), 'chs_structure_factor')
+        return ssum
+
+    def structure_factor_ms(self):
+        """Device time (ms) of the last `structure_factor`: [sweeps, transform, binning]."""
+        ms = np.zeros(3, dtype=np.float64)
+        self._check(self.lib.chs_structure_factor_last_ms(self._h, _dptr(ms)), 'chs_structure_factor_last_ms')
+        return ms
+
     @property
     def engine(self):
         return {CHS_ENGINE_DIRECT: 'direct', CHS_ENGINE_FAST: 'fast', CHS_ENGINE_CHIRP: 'chirp'}[self.lib.chs_engine(self._h)]
@@ -410,6 +429,15 @@ class Batch:
             self._check(self.lib.chs_batch_member_rows(self._h, m, _dptr(r), int(done[m])), 'chs_batch_member_rows')
             rows.append(r)
         return rows, status
+
+    def structure_factor(self, member=None):
+        """Ssum of one member ([nb]), or of all of them in one device pass ([B, nb]) for member=None
+        (chs_batch_structure_factor with member = -1)."""
+        nb = int(self.lib.chs_structure_factor_bins(self.N))
+        ssum = np.empty(nb if member is not None else (self.B, nb), dtype=np.float64)
+        self._check(self.lib.chs_batch_structure_factor(self._h, -1 if member is None else int(member), _dptr(ssum), nb),
+                    'chs_batch_structure_factor')
+        return ssum
 
     def get_state(self, member):
         s = chs_state()

@@ -233,6 +233,20 @@ class BatchSolver:
             raise AssertionError(f"member {m}: {e}")
         return self.solutions
 
+    def structure_factor(self, member=None):
+        """The members' radially averaged structure factors (`Solver.structure_factor`): a list of one
+        `spectrum.StructureFactor` per member from one device pass over the batch, or the one of ``member``.  Bit for
+        bit what the members' single Solvers return; the members' runs do not notice the look."""
+        from . import spectrum
+        b = self._get_batch()   # (EngineError without a device, like every compute call; no field yet: AssertionError)
+        for s in self.solvers:
+            s._push_edited_U()
+        if member is not None:
+            s = self.solvers[member]
+            return spectrum.StructureFactor(b.structure_factor(member), s.params.N, s.solution.delx)
+        ssum = b.structure_factor()
+        return [spectrum.StructureFactor(ssum[m], s.params.N, s.solution.delx) for m, s in enumerate(self.solvers)]
+
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""
         if self._batch is not None:

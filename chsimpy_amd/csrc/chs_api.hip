@@ -85,6 +85,7 @@ static void free_engine(Engine* E) {
   if (E->engine == CHS_ENGINE_CHIRP) chs_chirp_free(E);
   if (E->engine == CHS_ENGINE_FAST) chs_fast_free(E);
   chs_pointwise_free(E);
+  chs_spectrum_free(&E->spec);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
   hipFree(E->dT1); hipFree(E->dHat);
   if (E->dHat2) hipFree(E->dHat2);

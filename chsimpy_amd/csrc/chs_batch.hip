@@ -160,6 +160,7 @@ struct Batch {
   std::vector<BatchMember> hSeat;
   std::vector<long long> hQueue0;
   std::vector<std::vector<double>> qRows;  // the members' rows of the last queued call (chs_batch_member_rows)
+  void* spec = nullptr;          // chs_batch_structure_factor of all members: its buffers (chs_spectrum.hip), at the first call
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -175,6 +176,7 @@ void batch_free(Batch* b) {
     if (i < b->own.size() && b->own[i]) b->m[i]->stream = b->own[i];
     chs_destroy((chs_handle)b->m[i]);
   }
+  chs_spectrum_free(&b->spec);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -778,4 +780,13 @@ extern "C" int chs_batch_member_rows(chs_batch h, int32_t member, double* rows, 
   if (n > 0 && !rows) return bad("chs_batch_member_rows: rows is null");
   if (n > 0) std::memcpy(rows, v->data(), sizeof(double) * 9 * (size_t)n);
   return CHS_OK;
+}
+
+// The structure factor of one member -- the single handle's call on the batch's stream -- or of all of them at once.
+extern "C" int chs_batch_structure_factor(chs_batch h, int32_t member, double* ssum, int32_t nbins) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_structure_factor: null handle");
+  if (member < -1 || member >= b->B) return bad("chs_batch_structure_factor: no such member");
+  if (member >= 0) return chs_spectrum_one(b->m[(size_t)member], ssum, nbins, "chs_batch_structure_factor");
+  return chs_spectrum_all(b->m.data(), b->B, b->stream, b->chirp, &b->spec, ssum, nbins, "chs_batch_structure_factor");
 }

@@ -251,6 +251,7 @@ struct Engine {
   void* dD = nullptr;          // direct engine: orthonormal DCT-II matrix D[k][n]
   void* dTw = nullptr;         // fast engine: twiddle tables
   void* chirp = nullptr;       // chirp engine: its plan and tables (chs_chirp.hip)
+  void* spec = nullptr;        // structure factor: partial bins, result, events (chs_spectrum.hip), at the first call
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -344,6 +345,7 @@ int chs_launch_pre(Engine* E);                // partials -> state (L2, delt, ti
 int chs_launch_call_begin(Engine* E);         // entry of a solve_or_resume call: re-arm the loop, coefficients of params.delt
 int chs_launch_spectral(Engine* E, const void* hmu);  // dHat <- (dHat + Seig*hmu)/CHeig (natural order)
 int chs_launch_sum(Engine* E, int ignore_halt);  // meanU <- mean(dU)
+int chs_launch_sum_to(Engine* E, DevState* st);  // st->meanU <- mean(dU) for a state of the caller's, whatever E's halt flag
 int chs_launch_diag(Engine* E, int ignore_halt);  // dU -> diag partials
 int chs_launch_fin(Engine* E, int prepare_mode, int fused = 0);
 int chs_launch_jitter(Engine* E);
@@ -381,9 +383,19 @@ int chs_copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to);  // ro
 int chs_fast_init(Engine* E);
 void chs_fast_free(Engine* E);
 int chs_fast_dct2d(Engine* E, const void* in, void* out, bool inverse);  // natural in/out (tests)
+// out <- dctn(in), natural order, the row pass into `tmp` instead of T1: neither T1 nor hat_U is touched (out may be in)
+int chs_fast_dct2d_fwd_using(Engine* E, const void* in, void* out, void* tmp);
 int chs_fast_enter(Engine* E);   // hat_U <- dctn(U) in engine-native order (solver.py:159)
 int chs_fast_enter_fused(Engine* E);       // both of them with one sweep of U
 int chs_fast_enter_hat(Engine* E);         // hat_U <- dctn(U) alone: the first step's operand T1 is still on the device
 int chs_fast_prologue(Engine* E);          // T1 <- row DCT of EnergieEut(U) for the first step of a call
 int chs_fast_step(Engine* E, bool first, bool last); // [k_pre,] k_col, fused row kernel, k_step_tail
 int chs_fast_step_unfused(Engine* E);      // jitter path: every kernel separate, U complete in HBM
+
+// ---- structure factor (chs_spectrum.hip) -------------------------------------
+// Radially binned power of dctn(U - mean(U)) from the arrays that are dead between two calls.
+int chs_spectrum_one(Engine* E, double* ssum, int32_t nbins, const char* who);
+// all members of a batch (one stream `s`, one N and element type): sweep and binning launched once for all of them;
+// *buf is the batch's own buffer set, allocated here at the first call and freed by chs_spectrum_free
+int chs_spectrum_all(Engine* const* m, int B, hipStream_t s, bool chirp, void** buf, double* ssum, int32_t nbins, const char* who);
+void chs_spectrum_free(void** buf);

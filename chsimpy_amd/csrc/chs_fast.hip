@@ -168,6 +168,15 @@ int chs_fast_dct2d(Engine* E, const void* in, void* out, bool inverse) {
   return P->row_inv(E, ROW_INV_PLAIN, E->dT1, out, nullptr);
 }
 
+// The forward half of chs_fast_dct2d for a caller between two calls of a continuing loop (chs_spectrum.hip): T1 holds the
+// next step's operand and hat_U is carried then, so the row pass goes to `tmp`; k_col<FWD_NATURAL> writes `out` alone.
+int chs_fast_dct2d_fwd_using(Engine* E, const void* in, void* out, void* tmp) {
+  FastPlan* P = (FastPlan*)E->dTw;
+  int rc;
+  if ((rc = P->row_fwd(E, in, tmp, ROW_FWD_PLAIN))) return rc;
+  return P->col(E, MODE_FWD_NATURAL, tmp, nullptr, E->dHat, out);
+}
+
 // U <- idctn(hat_U) from k_col's native order: the field of the last completed step when the fused
 // row kernel has not been writing U (chs_fast_step) and a stop ended the call early.
 int chs_fast_recover_u(Engine* E) {

@@ -791,6 +791,17 @@ int chs_launch_sum(Engine* E, int ignore_halt) {
   return CHS_OK;
 }
 
+// the same reduction into a state of the caller's: the engine's own meanU, which a running loop hands from kernel to
+// kernel, stays what it is (chs_spectrum.hip)
+int chs_launch_sum_to(Engine* E, DevState* st) {
+  DISPATCH_T(E,
+    (k_sum<double><<<E->nBands, PW_THREADS, 0, E->stream>>>((const double*)E->dU, E->N, st, E->dPartSum, 1)),
+    (k_sum<float><<<E->nBands, PW_THREADS, 0, E->stream>>>((const float*)E->dU, E->N, st, E->dPartSum, 1)));
+  k_sum_fin<<<1, PW_THREADS, 0, E->stream>>>(E->dPartSum, E->nBands, E->N, st, 1);
+  CHS_HIP(hipGetLastError());
+  return CHS_OK;
+}
+
 int chs_launch_diag(Engine* E, int ignore_halt) {
   const dim3 grid((E->N + DIAG_BAND - 1) / DIAG_BAND, (E->N + PW_THREADS - 1) / PW_THREADS);
   chs_slot_begin(E, SLOT_DIAG);

@@ -123,13 +123,21 @@ def _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess):
             np.nan if fac_A0 is None else fac_A0, np.nan if fac_A1 is None else fac_A1)
 
 
-def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True):
-    """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126."""
+def _domain_row(sf):
+    """(k1, ell, ell_phys) of a member's final field (chsimpy_amd.spectrum.StructureFactor)."""
+    return (sf.k1, sf.ell, sf.ell_phys)
+
+
+def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None):
+    """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains`` (a dict): the
+    member's domain size, measured on the device behind its run, goes to ``domains[run_id]``."""
     from .simulator import Simulator
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
     try:
         solution = simulator.solve()
+        if domains is not None:
+            domains[run_id] = _domain_row(simulator.solver.structure_factor())
         simulator.export()
         rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
@@ -138,10 +146,11 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
     return rec
 
 
-def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None):
+def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
-    members run as a seat queue, that many at a time (None: all of them from the first step on)."""
+    members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``: as in
+    run_experiment_gpu, from one device pass over the group."""
     from .batch import BatchSolver
     from .simulator import Simulator
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
@@ -149,6 +158,9 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
     try:
         bs.prepare()
         solutions = bs.solve_or_resume()
+        if domains is not None:
+            for i, sf in zip(run_ids, bs.structure_factor()):
+                domains[i] = _domain_row(sf)
         recs = []
         for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
             # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
@@ -187,6 +199,34 @@ def gather_records(local, nr_items, rank, world, dist=None, device='cpu'):
     return sorted(recs, key=lambda r: r[9])
 
 
+def gather_domains(local, nr_items, rank, world, dist=None, device='cpu'):
+    """The members' (id, k1, ell, ell_phys) on every rank, ordered by run id: `local` maps this rank's run ids to
+    (k1, ell, ell_phys).  One all_gather of a (ceil(n/world), 4) float64 block per rank, as gather_records."""
+    rows = [(i,) + tuple(float(x) for x in v) for i, v in sorted(local.items())]
+    if world == 1 or dist is None:
+        return rows
+    import torch
+    per = (nr_items + world - 1) // world
+    buf = torch.full((per, 4), float('nan'), dtype=torch.float64, device=device)
+    for k, row in enumerate(rows):
+        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
+    out = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(out, buf)
+    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
+    return sorted((int(r[0]),) + r[1:] for r in got)
+
+
+def write_domains(file_id, rows):
+    """``<file_id>-domains.csv``: ``id, k1, ell, ell_phys`` per member (--domain-size), the floats written so that
+    they read back exactly."""
+    name = f"{file_id}-domains.csv"
+    with open(name, 'w') as f:
+        f.write("id,k1,ell,ell_phys\n")
+        for i, k1, ell, ell_phys in rows:
+            f.write(f"{int(i)},{float(k1)!r},{float(ell)!r},{float(ell_phys)!r}\n")
+    return name
+
+
 def write_metadata(file_id, ep, extra=()):
     """``<file_id>-metadata.csv`` (experiment.py:193-195): system information followed by the
     experiment parameters, one ``name, value`` per line."""
@@ -211,7 +251,7 @@ def write_results(file_id, records):
 
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
-                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256):
+                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -229,11 +269,16 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
     ``batch`` -- a member that stops hands its seat to the next one on the device, so the device does not run the tail
     of every group nearly empty.  Every member of a queue owns its device arrays from the start, so the runs are cut
     into queues of at most ``queue_members``; ``batch_fn`` is called once per queue.  A chirp batch has no queue:
-    ``queue`` at such an N runs member by member, with the note."""
+    ``queue`` at such an N runs member by member, with the note.
+
+    ``domains`` (a dict, with the default run functions): every member's domain size -- first moment k1 of the radially
+    averaged structure factor of its final field, the characteristic length 2N/k1 and that length in the solver's unit
+    -- is measured on the device behind its run and left in ``domains[run_id]`` for this rank's runs (gather_domains)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
+    dom = {} if domains is None else {'domains': domains}   # (the run functions are called as ever without it)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
-            return run_experiment_gpu(run_id, p, rv, al, U_init)
+            return run_experiment_gpu(run_id, p, rv, al, U_init, **dom)
     ids = my_run_ids(nr_items, rank, world)
     if batch > 0 and batch_fn is None:
         from .batch import scope_error
@@ -244,8 +289,8 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
         else:
             def batch_fn(run_ids, p, rv, al):
                 if queue:
-                    return run_batch_gpu(run_ids, p, rv, al, U_init, seats=batch)
-                return run_batch_gpu(run_ids, p, rv, al, U_init)
+                    return run_batch_gpu(run_ids, p, rv, al, U_init, seats=batch, **dom)
+                return run_batch_gpu(run_ids, p, rv, al, U_init, **dom)
     if batch > 0:
         local = []
         group = max(int(queue_members), 1) if queue else batch
@@ -320,6 +365,8 @@ def main(argv=None):
                     'a member that stops hands its seat to the next one on the device')
     ap.add_argument('--queue-members', type=int, default=256, help='members of one queue at the most (each owns its device '
                     'arrays from the start)')
+    ap.add_argument('--domain-size', action='store_true', help='measure every member\'s domain size on the device behind its '
+                    'run (radially averaged structure factor of the final field): <id>-domains.csv with id, k1, ell, ell_phys')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
     ap.add_argument('--backend', default=os.environ.get('CHS_DIST_BACKEND', 'nccl'),
@@ -370,10 +417,16 @@ def main(argv=None):
                        + ([f"batch_per_rank, {a.batch}"] if a.batch > 0 else [])
                        + ([f"queue_members, {a.queue_members}"] if (a.batch > 0 and a.queue) else [])
                        + (["dry_run, True"] if a.dry_run else []))
+    domains = {} if a.domain_size else None
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
                            batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
-                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members)
+                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains)
+    if domains is not None:
+        if a.dry_run:   # (members without device work: a function of the run id, as their records are)
+            nr = make_rand_values(ep)[2]
+            domains = {i: (1.0 + i, 2.0 * p.N / (1.0 + i), 2.0 * p.N / (1.0 + i) * p.L / (p.N - 1)) for i in my_run_ids(nr, rank, world)}
+        domain_rows = gather_domains(domains, make_rand_values(ep)[2], rank, world, dist, device)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)
@@ -381,6 +434,8 @@ def main(argv=None):
         print(f"  {p.file_id}-metadata.csv")
         print(f"  {p.file_id}-results-agg.csv")
         print(f"  {p.file_id}-results.csv")
+        if domains is not None:
+            print(f"  {write_domains(p.file_id, domain_rows)}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

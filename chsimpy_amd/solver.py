@@ -14,8 +14,8 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, mport
-from .solution import Solution
+from . import _lib, mport, spectrum
+from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
 
@@ -146,6 +146,24 @@ class Solver:
                 self.solution._bind_device_U(self.solution.__dict__.get('_U'), track=False)
             self._engine.close()
             self._engine = None
+
+    def _push_edited_U(self):
+        """The caller replaced the field since the last call -- by assignment, or by editing the array `solution.U`
+        handed out in place: `U = self.solution.U` (solver.py:158) is where the reference starts."""
+        sol = self.solution
+        if sol.__dict__.get('_U_dirty') or sol._host_edited():
+            u = sol.__dict__['_U']
+            self._engine.set_U(u)
+            sol.__dict__['_U_dirty'] = False
+            sol.__dict__['_U_print'] = _fingerprint(u)   # (the array mirrors the device field again: a later edit is noticed)
+
+    def structure_factor(self):
+        """The radially averaged structure factor of the field the device holds, a `spectrum.StructureFactor`
+        (Ssum, n, S, k1, ell, ell_phys).  Computed on the device between two calls without changing the run; a field
+        the host edited is pushed first, as solve_or_resume does.  Needs a field: prepare() first."""
+        eng = self._get_engine()
+        self._push_edited_U()
+        return spectrum.StructureFactor(eng.structure_factor(), self.params.N, self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

@@ -233,6 +233,25 @@ int chs_profile_steps(chs_handle h, int64_t nsteps, double ms[CHS_NKERNELS], int
 /* Device time (ms, HIP events on the handle's stream) of the last chs_step_n. */
 double chs_last_step_ms(chs_handle h);
 
+/* ---- Radially averaged structure factor of the current field ------------------------------
+ * C = dctn(U - mean(U), norm='ortho') through the handle's own transform engine; the power of mode (i, j) is C[i][j]^2,
+ * that of mode (0, 0) counts as 0.  The mode's bin is the integer nearest to sqrt(i^2 + j^2), decided in integer
+ * arithmetic: with s = i^2 + j^2 the one b with b^2 - b < s <= b^2 + b (b = 0 for s = 0; no tie exists).  Bins run
+ * 0 .. nb-1, nb = bin(N-1, N-1) + 1 = chs_structure_factor_bins(N); every mode is counted, the corners included.
+ * ssum[b] receives the sum of the power over the modes of bin b, float64 whatever the handle's element type.  How many
+ * modes a bin has is a function of N alone and left to the caller (chsimpy_amd/spectrum.py: bin_sizes, and S, k1 and
+ * the characteristic length 2N/k1 derived from ssum).
+ * Works on any handle that holds a field (else CHS_ESTATE) -- before and after chs_prepare, between two chs_step_n
+ * calls -- and is deterministic: two calls on one field return the same bits.  It uses only device arrays that are
+ * dead between two calls, so the run does not notice it: the chs_step_n that follows gives bit for bit what it gives
+ * behind a chs_get_U in the same place, a continued loop (see CHS_STEP_REDERIVE_HAT) included.
+ * nbins != chs_structure_factor_bins(N): CHS_EINVAL, the expected value in the message. */
+int32_t chs_structure_factor_bins(int32_t N);   /* nb(N); CHS_EINVAL for N outside [1, 16384] */
+int chs_structure_factor(chs_handle h, double* ssum, int32_t nbins);
+/* Device time (ms, HIP events) of the three parts of the handle's last chs_structure_factor: ms[0] the sweeps (mean,
+ * U - mean), ms[1] the transform, ms[2] the binning (both stages).  CHS_ESTATE before the first call. */
+int chs_structure_factor_last_ms(chs_handle h, double ms[3]);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -293,6 +312,12 @@ int chs_batch_set_state(chs_batch b, int32_t member, const chs_state* in);
 int chs_batch_step_n_queued(chs_batch b, int32_t seats, const int64_t* nsteps /*[R]*/, int32_t flags,
                             int64_t* steps_done /*[R]*/, int32_t* status /*[R]*/);
 int chs_batch_member_rows(chs_batch b, int32_t member, double* rows /*[n][9]*/, int64_t n);
+/* chs_structure_factor of member `member` (ssum[nbins]), or of every member for member = -1 (ssum[B][nbins]): the
+ * sweep and the binning are then launched once with the member as a grid dimension, the transform once per member
+ * (a chirp batch: once for all, four launches).  Member by member the result is bit for bit that of the member's single
+ * handle on the same field, and of the call with its own number.  The members' states, fields and records stay
+ * untouched: their next call is bit for bit what it is without the look. */
+int chs_batch_structure_factor(chs_batch b, int32_t member, double* ssum /*[nbins] or [B][nbins]*/, int32_t nbins);
 
 #ifdef __cplusplus
 }
