@@ -130,7 +130,7 @@ static DevState initial_state(const Engine* E) {
 static void read_env_hooks(Engine* E) {
   // with a stop rule armed a call usually ends early: shorter batches, fewer launches issued behind the stop
   // (a launch that finds the stop flag set costs ~2 us; the reference's default run stops at step 1674 of 1e6)
-  E->batchSteps = (!E->dc.full_sim || E->dc.time_limit_s > 0.0) ? CHS_STEPS_PER_BATCH / 4 : CHS_STEPS_PER_BATCH;
+  E->batchSteps = chs_stop_armed(E) ? CHS_STEPS_PER_BATCH / 4 : CHS_STEPS_PER_BATCH;
   if (const char* bs = getenv("CHS_BATCH_STEPS")) {  // test hook: small batches exercise the polling path
     const long v = atol(bs);
     if (v >= 1 && v <= CHS_ROWS_RING / 8) E->batchSteps = (int)v;
@@ -181,7 +181,7 @@ static int rearm(Engine* E, const chs_consts* c) {
   const DevState s0 = initial_state(E);
   CHS_HIP(hipMemcpy(E->dState, &s0, sizeof s0, hipMemcpyHostToDevice));
   E->prepared = false; E->have_U = false; E->hat_valid = false; E->resident = false;
-  E->stateCached = false; E->keepResident = false;
+  E->stateCached = false;
   E->jitter = 0.0; E->jitterPcg = false;
   if (E->dNoise) { hipFree(E->dNoise); E->dNoise = nullptr; }
   E->nColMinCur = 0; E->lastStepMs = 0.0; E->timer.on = false;
@@ -465,12 +465,12 @@ static int enter(Engine* E) {
 }
 
 // one iteration of solver.py:165-249
-static int one_step(Engine* E, bool first, bool last) {
+static int one_step(Engine* E, const StepMode& mode, bool first, bool last) {
   int rc;
-  const bool jitter = (E->dNoise || E->jitterPcg) && E->jitter > 0.0 && E->jitter < 0.1;
+  const bool jitter = chs_jitter_on(E);
   if (E->engine == CHS_ENGINE_FAST && !jitter) {
     // fused pipeline: k_col, k_row_inv (+ record partials + next step's row pass), k_step_tail
-    return chs_fast_step(E, first, last);
+    return chs_fast_step(E, mode, first, last);
   }
   if (chs_natural_engine(E)) {
     if ((rc = chs_launch_mu(E))) return rc;        // 166-175
@@ -516,9 +516,10 @@ int chs_copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to) {
 }
 
 // Did the energy rule or the time limit end a call of nsteps steps before its last step, with the fused row kernel
-// keeping U in registers?  Then hat_U is that of the last completed step and the field is to be rebuilt from it.
-bool chs_stopped_short(const Engine* E, const DevState& s, int64_t nsteps) {
-  return s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !E->storeU && s.rows_written < nsteps;
+// keeping U in registers (stored_u false)?  Then hat_U is that of the last completed step and the field is to be
+// rebuilt from it.  (A call of no steps never stopped short.)
+bool chs_stopped_short(const DevState& s, int64_t nsteps, bool stored_u) {
+  return s.halt && s.stop_reason != CHS_STOP_NONE && !s.nan_flag && !stored_u && s.rows_written < nsteps;
 }
 
 // U <- idctn(hat_U) of a call that stopped short (solver.py:197-199 breaks before U is updated, 242-251 returns the U
@@ -555,47 +556,33 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
   E->timer.on = false;  // the entry work is not a per-step kernel
   // a new call re-arms the loop and reloads the coefficients of params.delt (k_call_begin)
   if ((rc = chs_launch_call_begin(E))) return rc;
-  const bool fused = (E->engine == CHS_ENGINE_FAST) && !((E->dNoise || E->jitterPcg) && E->jitter > 0.0 && E->jitter < 0.1);
-  const bool derive = !((flags & CHS_STEP_CARRY_HAT) && E->hat_valid);
-  // Fixed time step on the fused pipeline: the last step of a call leaves hat_U, the row transform of
-  // EnergieEut(U) and its sum of squares on the device, and a call that finds them continues the loop where it
-  // stopped -- hat_U is the array the reference would recompute as dctn(idctn(hat_U)) (solver.py:159), equal up
-  // to rounding; CHS_STEP_REDERIVE_HAT asks for the literal recomputation.
-  // A caller that asks for the literal re-derivation (CHS_STEP_REDERIVE_HAT) gets hat_U = dctn(U) recomputed at every
-  // call; what such a call still takes over from its predecessor is the OTHER thing the last fused step leaves: T1 = the
-  // row transform of EnergieEut(U) and its sum of squares -- a function of the unchanged field U alone, which k_row_fwd2
-  // would only compute again bit for bit -- when the caller allows it (CHS_STEP_KEEP_T1; off by default: measured, it
-  // buys nothing at N=4096 -- the entry shrinks from 215 to 152 us, the call's last step, now the fused kernel, grows by
-  // as much: profiles/r04_ab_entry.txt).
-  const bool keep_t1 = (flags & CHS_STEP_KEEP_T1) != 0;
-  const bool rederive = (flags & CHS_STEP_REDERIVE_HAT) != 0;
-  E->keepResident = fused && !E->dc.adaptive_time && !profile && !(flags & CHS_STEP_LAST_CALL) && (!rederive || keep_t1);
-  const bool cont = fused && E->resident && E->hat_valid && !rederive && !profile;
-  const bool cont_t1 = fused && E->resident && rederive && keep_t1 && !profile;
-  if (nsteps > 0) E->resident = false;
-  if (cont && nsteps > 0) {
-    // nothing to do: T1, partMu and hat_U are in place
-  } else if (cont_t1 && nsteps > 0) {
-    // hat_U = dctn(U), literally; T1 and partMu are in place
-    if ((rc = chs_fast_enter_hat(E))) return rc;
-    E->hat_valid = true;
-  } else if (derive && fused && nsteps > 0) {
-    // hat_U = dctn(U) and the first step's row transform of EnergieEut(U) from one sweep of U
-    if ((rc = chs_fast_enter_fused(E))) return rc;
-    E->hat_valid = true;
-  } else {
-    if (derive) {
-      if ((rc = enter(E))) return rc;
-    }
-    E->hat_valid = true;
-    E->timer.on = profile;
-    if (fused && nsteps > 0) {
-      if ((rc = chs_fast_prologue(E))) { E->timer.on = false; return rc; }
-    }
+  // how the call is entered and what its steps issue: chs_step_host.h
+  CallFacts f;
+  f.adaptive = E->dc.adaptive_time != 0; f.full_sim = E->dc.full_sim != 0; f.time_limit_s = E->dc.time_limit_s; f.N = E->N;
+  f.fused = (E->engine == CHS_ENGINE_FAST) && !chs_jitter_on(E);
+  f.fusedAdapt = E->fusedAdapt; f.partRows = E->dPartColRows != nullptr; f.twoSets = E->partSet[0][0] != nullptr;
+  f.adaptSparse = E->adaptSparse; f.lamByColmin = E->lamByColmin; f.gateEarly = E->gateEarly;
+  f.profile = profile;
+  f.carry_hat = (flags & CHS_STEP_CARRY_HAT) != 0; f.rederive = (flags & CHS_STEP_REDERIVE_HAT) != 0;
+  f.keep_t1 = (flags & CHS_STEP_KEEP_T1) != 0; f.last_call = (flags & CHS_STEP_LAST_CALL) != 0;
+  f.nsteps = nsteps; f.resident = E->resident; f.hat_valid = E->hat_valid;
+  const bool fused = f.fused;
+  const StepMode mode = step_mode(f);
+  const CallEntry entry = call_entry(f);
+  E->resident = entry.resident;
+  E->pending = {};
+  switch (entry.kind) {
+    case ENTRY_CONTINUE: break;
+    case ENTRY_HAT_ONLY: if ((rc = chs_fast_enter_hat(E))) return rc; break;
+    case ENTRY_FUSED: if ((rc = chs_fast_enter_fused(E))) return rc; break;
+    default:
+      if (entry.derive && (rc = enter(E))) return rc;
+      E->timer.on = profile;
+      if (entry.prologue && (rc = chs_fast_prologue(E))) { E->timer.on = false; return rc; }
   }
+  E->hat_valid = entry.hat_valid;
   E->timer.on = profile;
-  E->dHatCall = E->dHat;  // (chs_fast_step may alternate two hat_U buffers from here on)
-  E->hatFlip = false;
+  void* const hat_call = E->dHat;  // (with mode.hatFlip the steps alternate two hat_U buffers from here on)
   int64_t issued = 0, copied = 0;
   int batch = 0;
   bool stopped = false;
@@ -603,7 +590,7 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
     int64_t nb = nsteps - issued;
     if (nb > E->batchSteps) nb = E->batchSteps;
     for (int64_t s = issued; s < issued + nb; ++s) {
-      if ((rc = one_step(E, s == 0, s == nsteps - 1))) { E->timer.on = false; return rc; }
+      if ((rc = one_step(E, mode, s == 0, s == nsteps - 1))) { E->timer.on = false; return rc; }
       if (profile && (s % 32) == 31) timer_harvest(E);
     }
     issued += nb;
@@ -642,24 +629,21 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
     // advanced by the steps that did finish, so nothing on the device is a consistent state to step on from --
     // the next chs_step_n returns CHS_ESTATE until chs_set_U / chs_init_U_pcg64 and chs_prepare have run.
     E->hat_valid = false; E->resident = false; E->stateCached = false;
-    E->tailDeferred = false; E->tailGated = false;
     E->prepared = false; E->have_U = false; E->csHost = -1;
     if (steps_done) *steps_done = 0;
     chs_set_error("internal: a workgroup gave up waiting for the step's bookkeeping (gated tail)");
     return CHS_EHIP;
   }
-  if (E->hatFlip) {
-    // two hat_U buffers alternated per ISSUED step; the one that holds the state behind the steps that were
-    // COMPLETED is the call's first one after an even number of them, the other one after an odd number
-    void* other = (E->dHat == E->dHatCall) ? E->dHat2 : E->dHat;
-    const bool even = ((s.rows_written < nsteps ? s.rows_written : nsteps) & 1) == 0;
-    void* valid = even ? E->dHatCall : other;
-    E->dHat2 = (valid == E->dHatCall) ? other : E->dHatCall;
-    E->dHat = valid;
+  if (mode.hatFlip && nsteps > 0) {
+    // two hat_U buffers alternated per ISSUED step: dHat becomes the one behind the COMPLETED steps
+    void* other = (E->dHat == hat_call) ? E->dHat2 : E->dHat;
+    const bool first_one = hat_after_flip(s.rows_written < nsteps ? s.rows_written : nsteps) == 0;
+    E->dHat = first_one ? hat_call : other;
+    E->dHat2 = first_one ? other : hat_call;
   }
-  if (fused && chs_stopped_short(E, s, nsteps) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
+  if (fused && chs_stopped_short(s, nsteps, mode.storesU) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
   if (s.halt) E->hat_valid = false;  // (a deferred tail lets k_col run once past a NaN stop)
-  if (nsteps > 0) E->resident = E->keepResident && !s.halt && s.rows_written >= nsteps;
+  if (nsteps > 0) E->resident = mode.keepResident && !s.halt && s.rows_written >= nsteps;
   E->stateCached = true;  // (the recovery above leaves the device state equal to s)
   E->csHost = s.computed_steps;
   int64_t done = s.rows_written;

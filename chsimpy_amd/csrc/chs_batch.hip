@@ -411,9 +411,9 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
     r.st = E->dState;   // (rows_written >= nsteps = 0 keeps the member out of every launch)
     if (n == 0) continue;
     if (!E->dRows) return bad(who + ": member " + std::to_string(i) + " has no rows ring");
-    E->stateCached = false; E->resident = false; E->keepResident = false;
+    E->stateCached = false; E->resident = false;
     c.cs0[(size_t)i] = E->csHost;
-    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
+    if (chs_stop_armed(E)) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
     if ((rc = chs_launch_call_begin(E))) return rc;
     E->hat_valid = true;
     r.dc = E->dc;
@@ -431,11 +431,9 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
     c.status[i] = CHS_OK;
     r.st = E->dState;   // (read by every batched kernel: rows_written >= nsteps = 0 keeps the member out)
     if (n == 0) continue;   // sits the call out (a queue never seats it): state and field stay as they are
-    E->stateCached = false; E->resident = false; E->keepResident = false;
-    E->tailDeferred = false; E->tailGated = false; E->preRider = false;
-    E->storeU = c.adaptive && !c.fused;   // (the sweep of U needs the field of every step: chs_fast_step)
+    E->stateCached = false; E->resident = false;
     c.cs0[(size_t)i] = E->csHost;
-    if (!E->dc.full_sim || E->dc.time_limit_s > 0.0) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
+    if (chs_stop_armed(E)) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
     if ((rc = chs_launch_call_begin(E))) return rc;
     if ((rc = chs_fast_enter_fused(E))) return rc;   // (selects the partial-sum set the whole call uses)
     E->hat_valid = true;
@@ -537,9 +535,10 @@ int call_finish(BatchCall& c) {
       chs_set_error(std::string(c.who) + ": member " + std::to_string(i) + " was left with steps to do");
       return CHS_ESTATE;
     }
-    // its row kernel has been keeping U in registers -- the member's own arrays, whoever has its seat by now
+    // its row kernel has been keeping U in registers -- the member's own arrays, whoever has its seat by now -- unless
+    // the step-size sums come from a sweep of U, which needs the field of every step (fused_row_mode)
     // (a chirp member stores U every step: what it holds after a stop is the field of its last completed step)
-    if (!b->chirp && chs_stopped_short(E, s, c.nsteps[i]) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
+    if (!b->chirp && chs_stopped_short(s, c.nsteps[i], c.adaptive && !c.fused) && (rc = chs_rebuild_stopped_u(E, s))) return rc;
     if (s.halt) E->hat_valid = false;
     E->csHost = s.computed_steps;
     const int64_t done = s.rows_written < c.nsteps[i] ? s.rows_written : c.nsteps[i];
@@ -622,8 +621,7 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
   if (maxn > 0 && !adaptive) {
     if ((rc = launch_tail(b->stream, b->dMem, B, P->col_threads, false, 1))) return rc;
   }
-  const int fuse_mode = fused ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED;
-  const int store_u = (adaptive && !fused) ? 1 : 0;
+  const RowMode rm = fused_row_mode(adaptive, fused);
   int64_t issued = 0;
   bool stopped = false;
   while (issued < maxn && !stopped) {
@@ -636,7 +634,7 @@ extern "C" int chs_batch_step_n(chs_batch h, const int64_t* nsteps, int32_t flag
         last |= s == nsteps[i] - 1;
       }
       if ((rc = P->col_batch(E0, b->stream, b->dMem, B, (s & 1) ? 1 : 0))) return rc;
-      if (go_on && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, fuse_mode, store_u))) return rc;
+      if (go_on && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, rm.mode, rm.store_u))) return rc;
       if (last && (rc = P->row_inv_batch(E0, b->stream, b->dMem, B, ROW_INV_DIAG, 1))) return rc;
       if (adaptive && go_on) {
         // the column minimum of the coming step's integrand, for the members whose rule fires (the kernels check again)
@@ -710,8 +708,7 @@ extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t
     k_seat_batch<<<1, 64, 0, b->stream>>>(b->dSeat, S, b->dMem, R, b->dQueue, 0);
     CHS_HIP(hipGetLastError());
   }
-  const int fuse_mode = fused ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED;
-  const int store_u = (adaptive && !fused) ? 1 : 0;
+  const RowMode rm = fused_row_mode(adaptive, fused);
   QueueMembers qm(nsteps, R, S);
   bool all_seated = running <= S;                 // nobody waits (any more): no seat changes hands
   int64_t issued = 0;
@@ -723,7 +720,7 @@ extern "C" int chs_batch_step_n_queued(chs_batch h, int32_t seats, const int64_t
     for (int64_t s = issued; s < issued + nb; ++s) {
       const bool last = qm.last_pair(s);   // may the call of an unfinished member end with this step?
       if ((rc = P->col_batch(E0, b->stream, b->dSeat, S, (s & 1) ? 1 : 0))) return rc;
-      if ((rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, fuse_mode, store_u))) return rc;
+      if ((rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, rm.mode, rm.store_u))) return rc;
       if (last && (rc = P->row_inv_batch(E0, b->stream, b->dSeat, S, ROW_INV_DIAG, 1))) return rc;
       if (adaptive) {
         if (fused) {

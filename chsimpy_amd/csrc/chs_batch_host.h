@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <vector>
 
+#include "chs_step_host.h"
+
 // The global step count of a queued call when no member stops early: the members take the seats in member order, a
 // seat changes hands in front of an even step (k_seat_batch).  A member that stops early only lets the ones behind it
 // start sooner, so this bounds the steps to issue; with as many seats as members it is the largest nsteps.
@@ -29,7 +31,7 @@ inline bool batch_rule_fires(long long cs0, int64_t n, int64_t s) {
   if (s >= n - 1) return false;           // no step behind s: no time-step control
   if (cs0 < 0) return true;
   const long long cs_next = cs0 + s + 1;  // (chs_tail.h: cs_next; a halted member's kernels are no-ops)
-  return cs_next > 500 && (cs_next % 2) == 0;
+  return rule_fires(cs_next);
 }
 
 // What the host of a queued call knows of its members, from the polls alone.  The last-step pair of member i belongs

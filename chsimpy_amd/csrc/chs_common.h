@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "chs_hip.h"
+#include "chs_step_host.h"
 
 #define CHS_WAVE 64
 
@@ -228,13 +229,11 @@ struct Engine {
                            // next call continues without an entry pass (the last fused step left them, chs_fast_step)
   bool lamByColmin = true;    // CHS_LAM_BY_COLMIN (chs_fast_rearm): the reduction's last block sets the coming step's coefficients
   bool gateEarly = false;     // CHS_GATE_EARLY=1 (chs_fast_rearm): experiment, measured equal
-  bool tailEarly = false;     // the gated bookkeeping of the coming k_col publishes its coefficients ahead of the record
   bool adaptSparse = true;    // CHS_ADAPT_SPARSE (chs_fast_rearm)
   long long csHost = -1;      // the device's computed_steps as the host can follow it (prepare / set_state / end of a call, +1 per
                               // issued step): lets the adaptive path issue the step-size machinery only on the steps whose rule
                               // fires (chs_fast_step); -1 = not known
   bool stateCached = false;   // hState[0] is the device state as the last call left it (chs_get_state without a round trip)
-  bool keepResident = false;  // this call's last step runs the fused row kernel so that the next call can continue
 
   // device buffers (element type per dtype)
   void* dU = nullptr;      // field U, row-major N x N
@@ -243,8 +242,6 @@ struct Engine {
   void* dT2 = nullptr;     // transform scratch
   void* dHat = nullptr;    // hat_U (direct: natural order; fast: engine-native order)
   void* dHat2 = nullptr;   // second hat_U buffer of the small grids' stop-rule runs (chs_fast_step), allocated on demand
-  void* dHatCall = nullptr;  // ... the buffer hat_U was in when the running call began
-  bool hatFlip = false;    // ... this call alternates the two
   void* dNoise = nullptr;  // jitter noise (optional)
   double jitter = 0.0;
   double* dLambda = nullptr;   // lam_i, N doubles
@@ -276,11 +273,9 @@ struct Engine {
   // the partial sums ping-pong between two sets so that step s+1 does not overwrite what it reads
   double* partSet[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};  // Diag, Mu, E2, Ra
   int parity = 0;
-  bool tailDeferred = false;  // the tail of the previous step is still to run
-  bool tailGated = false;     // ... and the other workgroups of that k_col wait for its decision (stop rules, adaptive dt)
+  PendingTail pending;        // the tail of the previous step of the running call, where it is still to run (chs_fast_step)
   unsigned long long gateSeq = 0;
   bool testGateWithhold = false;  // test hook (CHS_TEST_GATE_WITHHOLD=1, read by chs_step_n in builds with -DCHS_TEST_HOOKS=1): gated tails never publish
-  bool preRider = false;      // the first step's time-step control rides in its k_col (deferred-tail mode)
   unsigned stepCount = 0;     // k_col<MODE_STEP> launches so far (tile walk direction alternates)
   // jitter noise generated on the device: numpy's PCG64 stream continued from the host generator's state
   bool jitterPcg = false;
@@ -289,8 +284,6 @@ struct Engine {
   bool fusedAdapt = false;    // the fused row kernel adds up the adaptive-step integrand itself
   void* dPartColRows = nullptr;    // [nRowBlocks][N] partial column sums of that integrand, in the engine's element type
   double* dColSlices = nullptr;    // [CS_SLICES][N] first stage of their reduction (chs_launch_colmin_rows)
-  bool storeU = true;         // the fused row kernel writes U on intermediate steps (chs_fast_step)
-  int tailSet = 0;            // ... on this partial set
   hipEvent_t evA = nullptr, evB = nullptr;
   // pinned host mirror of the device state: slot 0 = the state at the end of a call, slots 1..4 = the
   // polls behind the batches of a long call (run_steps)
@@ -365,6 +358,11 @@ int chs_chirp_init(Engine* E);
 void chs_chirp_free(Engine* E);
 int chs_chirp_dct2d(Engine* E, const void* in, void* out, void* tmp, bool inverse);
 
+// can the energy rule or the time limit end the run; does the run perturb U between the inverse transform and the
+// record (solver.py:210-211: no fusion across the perturbation)
+inline bool chs_stop_armed(const Engine* E) { return stop_armed(E->dc.full_sim != 0, E->dc.time_limit_s); }
+inline bool chs_jitter_on(const Engine* E) { return (E->dNoise || E->jitterPcg) && E->jitter > 0.0 && E->jitter < 0.1; }
+
 // The direct and the chirp engine are one family: natural order in every array, the unfused step of chs_api.hip
 // (one_step); they differ in dct2d alone.
 inline bool chs_natural_engine(const Engine* E) { return E->engine == CHS_ENGINE_DIRECT || E->engine == CHS_ENGINE_CHIRP; }
@@ -376,8 +374,9 @@ inline int chs_natural_dct2d(Engine* E, const void* in, void* out, void* tmp, bo
 bool chs_fast_supported(int N, int dtype);
 int chs_fast_recover_u(Engine* E);  // U <- idctn(hat_U): the field of the last completed step
 // (chs_api.hip, shared by chs_step_n and the batch) a call that the energy rule or the time limit ended before its last
-// step: the test, and the rebuild of the field through chs_fast_recover_u around the fetched state s
-bool chs_stopped_short(const Engine* E, const DevState& s, int64_t nsteps);
+// step: the test (stored_u: the row kernel wrote the field on every step, nothing to rebuild), and the rebuild of the
+// field through chs_fast_recover_u around the fetched state s
+bool chs_stopped_short(const DevState& s, int64_t nsteps, bool stored_u);
 int chs_rebuild_stopped_u(Engine* E, const DevState& s);
 int chs_copy_rows_out(Engine* E, double* rows, int64_t from, int64_t to);  // rows [from, to) of the ring -> rows[from*9 ...]
 int chs_fast_init(Engine* E);
@@ -389,7 +388,7 @@ int chs_fast_enter(Engine* E);   // hat_U <- dctn(U) in engine-native order (sol
 int chs_fast_enter_fused(Engine* E);       // both of them with one sweep of U
 int chs_fast_enter_hat(Engine* E);         // hat_U <- dctn(U) alone: the first step's operand T1 is still on the device
 int chs_fast_prologue(Engine* E);          // T1 <- row DCT of EnergieEut(U) for the first step of a call
-int chs_fast_step(Engine* E, bool first, bool last); // [k_pre,] k_col, fused row kernel, k_step_tail
+int chs_fast_step(Engine* E, const StepMode& mode, bool first, bool last); // [k_pre,] k_col, fused row kernel, k_step_tail: step_issue
 int chs_fast_step_unfused(Engine* E);      // jitter path: every kernel separate, U complete in HBM
 
 // ---- structure factor (chs_spectrum.hip) -------------------------------------

@@ -130,9 +130,8 @@ int chs_fast_rearm(Engine* E) {
     E->dPartDiag = E->partSet[0][0]; E->dPartMu = E->partSet[0][1];
     E->dPartE2 = E->partSet[0][2]; E->dPartRa = E->partSet[0][3];
   }
-  E->parity = 0; E->tailSet = 0;
-  E->tailDeferred = false; E->tailGated = false; E->preRider = false;
-  E->stepCount = 0; E->storeU = true;
+  E->parity = 0;
+  E->stepCount = 0;
   return CHS_OK;
 }
 
@@ -162,10 +161,10 @@ int chs_fast_dct2d(Engine* E, const void* in, void* out, bool inverse) {
   int rc;
   if (!inverse) {
     if ((rc = P->row_fwd(E, in, E->dT1, ROW_FWD_PLAIN))) return rc;
-    return P->col(E, MODE_FWD_NATURAL, E->dT1, nullptr, E->dHat, out);
+    return P->col(E, MODE_FWD_NATURAL, E->dT1, nullptr, E->dHat, out, no_rider());
   }
-  if ((rc = P->col(E, MODE_INV_NATURAL, nullptr, E->dT1, E->dHat, (void*)in))) return rc;
-  return P->row_inv(E, ROW_INV_PLAIN, E->dT1, out, nullptr);
+  if ((rc = P->col(E, MODE_INV_NATURAL, nullptr, E->dT1, E->dHat, (void*)in, no_rider()))) return rc;
+  return P->row_inv(E, ROW_INV_PLAIN, E->dT1, out, nullptr, 1);
 }
 
 // The forward half of chs_fast_dct2d for a caller between two calls of a continuing loop (chs_spectrum.hip): T1 holds the
@@ -174,7 +173,7 @@ int chs_fast_dct2d_fwd_using(Engine* E, const void* in, void* out, void* tmp) {
   FastPlan* P = (FastPlan*)E->dTw;
   int rc;
   if ((rc = P->row_fwd(E, in, tmp, ROW_FWD_PLAIN))) return rc;
-  return P->col(E, MODE_FWD_NATURAL, tmp, nullptr, E->dHat, out);
+  return P->col(E, MODE_FWD_NATURAL, tmp, nullptr, E->dHat, out, no_rider());
 }
 
 // U <- idctn(hat_U) from k_col's native order: the field of the last completed step when the fused
@@ -182,8 +181,8 @@ int chs_fast_dct2d_fwd_using(Engine* E, const void* in, void* out, void* tmp) {
 int chs_fast_recover_u(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
   int rc;
-  if ((rc = P->col(E, MODE_INV_NATIVE, nullptr, E->dT1, E->dHat, nullptr))) return rc;
-  return P->row_inv(E, ROW_INV_PLAIN, E->dT1, E->dU, nullptr);
+  if ((rc = P->col(E, MODE_INV_NATIVE, nullptr, E->dT1, E->dHat, nullptr, no_rider()))) return rc;
+  return P->row_inv(E, ROW_INV_PLAIN, E->dT1, E->dU, nullptr, 1);
 }
 
 // hat_U <- dctn(U) in k_col's native order (solver.py:159)
@@ -191,7 +190,7 @@ int chs_fast_enter(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
   int rc;
   if ((rc = P->row_fwd(E, E->dU, E->dT1, ROW_FWD_PLAIN))) return rc;
-  return P->col(E, MODE_FWD_NATIVE, E->dT1, nullptr, E->dHat, nullptr);
+  return P->col(E, MODE_FWD_NATIVE, E->dT1, nullptr, E->dHat, nullptr, no_rider());
 }
 
 // T1 <- row DCT-II of EnergieEut(U): what the fused row kernel of the previous step would
@@ -208,7 +207,6 @@ static void select_partial_set(Engine* E) {
 // one sweep of U instead of two (k_row_fwd2), the row transform of U parked in the idle T2 buffer.
 int chs_fast_enter_fused(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
-  E->tailDeferred = false;
   select_partial_set(E);
   int rc;
   chs_slot_begin(E, SLOT_MU);
@@ -219,7 +217,7 @@ int chs_fast_enter_fused(Engine* E) {
   // order too (descending -- what was written last is read first -- measured 2.3 % slower on a literal 20-step call,
   // profiles/r04_ab_dma.txt), whatever the parity of the steps of earlier calls; then the directions alternate
   E->stepCount = 0;
-  return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr);
+  return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr, no_rider());
 }
 
 // Entry of a literal call that finds the first step's operand on the device: the previous call's last step was the fused
@@ -234,12 +232,11 @@ int chs_fast_enter_hat(Engine* E) {
   // (ordinary cached stores: this kernel 86 us at N=4096 fp64 against 190-210 us with non-temporal ones, profiles/r04_ab_entry.txt)
   if ((rc = P->row_fwd(E, E->dU, E->dT2, ROW_FWD_PLAIN))) return rc;
   E->stepCount = 0;
-  return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr);
+  return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr, no_rider());
 }
 
 int chs_fast_prologue(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
-  E->tailDeferred = false;
   select_partial_set(E);  // sum(mu^2) must land where the first step's k_pre looks for it
   chs_slot_begin(E, SLOT_MU);
   const int rc = P->row_fwd(E, E->dU, E->dT1, ROW_FWD_POINTWISE);
@@ -248,121 +245,44 @@ int chs_fast_prologue(Engine* E) {
 }
 
 // One timestep on the fused pipeline.  On entry T1 holds the row transform of
-// EnergieEut(U_k) and partMu its sum of squares; on exit U_(k+1) is in HBM, the pointwise
-// diagnostics partials of U_(k+1) are ready for k_fin and, with fuse_next, T1/partMu are
-// ready for the next step.
-// full_sim, fixed time step, no time limit: the tail of step s decides nothing the column pass of
-// step s+1 needs.  It is deferred and rides as one extra workgroup in k_col of step s+1 -- no launch
-// of its own, nothing waits for it.  Only NaN can stop such a run (one kernel later; the field is
-// unspecified then anyway).  The partial sums alternate between two sets.
-// Stop rules on the small grids (CHS_HAT_FLIP_MAX_N, fixed time step): k_col reads hat_U from one buffer and writes
-// the other, alternating from step to step, so the tail can stay deferred -- when it stops the run, the buffer
-// the carrying k_col READ is the state of the last completed step (run_steps points dHat at it and rebuilds U).
-// The tiles of a small grid reach a gate before the riding tail has decided (N=512: 26.5 against 23.9 us/step);
-// at N=4096 the gate costs 1 % and a third 134 MB array would not fit beside T and hat_U in the Infinity Cache.
-#ifndef CHS_HAT_FLIP_MAX_N
-#define CHS_HAT_FLIP_MAX_N 2048
-#endif
-static bool hat_flip(const Engine* E) {
-  return !E->dc.adaptive_time && (!E->dc.full_sim || E->dc.time_limit_s > 0.0) && E->N <= CHS_HAT_FLIP_MAX_N &&
-         !E->timer.on && E->partSet[0][0] != nullptr;
-}
-static bool can_defer_tail(const Engine* E) {
-  return !E->dc.adaptive_time && ((!(E->dc.time_limit_s > 0.0) && E->dc.full_sim) || hat_flip(E)) && !E->timer.on &&
-         E->partSet[0][0] != nullptr;
-}
-// Between the steps of a call nothing reads U from HBM (the adaptive step included, once the fused
-// row kernel adds up its integrand), so the fused row kernel keeps it in registers.  Whenever a stop
-// can end the call early (energy rule, time limit) the tail runs in stream order right behind the
-// row kernel: hat_U is then still that of the last completed step and run_steps() rebuilds
-// U = idctn(hat_U) once (chs_fast_recover_u).
-static bool fused_adaptive(const Engine* E) {
-  return E->dc.adaptive_time && E->fusedAdapt && E->dPartColRows != nullptr;
-}
-static bool can_skip_u(const Engine* E) {
-  return !E->dc.adaptive_time || fused_adaptive(E);
-}
-
-int chs_fast_step(Engine* E, bool first, bool last) {
+// EnergieEut(U_k) and partMu its sum of squares; on exit U_(k+1) is in HBM (or, inside a call, in the row kernel's
+// registers alone), the pointwise diagnostics partials of U_(k+1) are ready for k_fin and, on every step but a call's
+// last, T1/partMu are ready for the next step.  What goes out is decided in chs_step_host.h (step_issue, with the
+// reasons for every mode next to the fields of StepMode); this function executes it.
+int chs_fast_step(Engine* E, const StepMode& mode, bool first, bool last) {
   FastPlan* P = (FastPlan*)E->dTw;
   int rc;
-  const bool defer = can_defer_tail(E);
-  E->storeU = !can_skip_u(E);
+  const StepIssue p = step_issue(mode, E->csHost, first, last);
   select_partial_set(E);
-  if (first) {
-    // time-step control of the first step of the call; later steps get it from the tail.
-    // The prologue wrote sum(mu^2) into the set that was current then: fold it in here.
-    if (E->dc.adaptive_time) {
-      if ((rc = chs_launch_mu_colsums(E, 0))) return rc;
-    }
-    if (defer) {
-      E->preRider = true;  // rides as the extra workgroup of this step's k_col (no launch of its own)
-    } else {
-      if ((rc = chs_launch_pre(E))) return rc;
-    }
-  }
+  if (p.sweep0 && (rc = chs_launch_mu_colsums(E, 0))) return rc;
+  if (p.pre == PRE_LAUNCH && (rc = chs_launch_pre(E))) return rc;
+  // the extra workgroup of this step's k_col: the first step's time-step control or the previous step's tail
+  const ColRider rider = p.pre == PRE_RIDES ? pre_rider() : tail_rider(E->pending);
+  E->pending = {};
   chs_slot_begin(E, SLOT_SPEC);
   // T2 (columns inverted) overwrites T1 in place: every workgroup of k_col reads exactly the part
   // of the tile it later writes, every workgroup of the fused row kernel likewise for its rows --
   // one array less in the per-step working set (T + hat_U = 268 MB next to a 256 MB Infinity Cache)
   void* T2 = E->dT1;
-  if (hat_flip(E)) {
+  if (p.flip) {
     if (!E->dHat2) CHS_HIP(hipMalloc(&E->dHat2, (size_t)E->N * E->N * E->esz));
-    E->hatFlip = true;
-    rc = P->col(E, MODE_STEP, E->dT1, T2, E->dHat, E->dHat2);  // + the previous step's deferred tail
+    rc = P->col(E, MODE_STEP, E->dT1, T2, E->dHat, E->dHat2, rider);
     void* t = E->dHat; E->dHat = E->dHat2; E->dHat2 = t;      // the next step reads what this one writes
   } else {
-    rc = P->col(E, MODE_STEP, E->dT1, T2, E->dHat, nullptr);  // + the previous step's deferred tail
+    rc = P->col(E, MODE_STEP, E->dT1, T2, E->dHat, nullptr, rider);
   }
   chs_slot_end(E, SLOT_SPEC);
-  E->tailDeferred = false;
   if (rc) return rc;
   chs_slot_begin(E, SLOT_INV);
-  const bool fa = fused_adaptive(E);
-  // Adaptive step with the host able to follow the step counter: the step-size rule fires on every second step beyond
-  // step 500 only (solver.py:177), and only THOSE steps need the column sums reduced and the next k_col gated (its
-  // coefficients change).  On the others -- with nothing else armed that a tail could decide -- the reduction launches are
-  // not issued at all (they used to return at once: two empty launches per step) and the bookkeeping rides ungated.
-  // (CHS_ADAPT_SPARSE=0: as before round 4.)
-  bool fires = true;
-  if (E->dc.adaptive_time && E->csHost >= 0 && E->adaptSparse) {
-    const long long cs_next = E->csHost + 1;          // the counter behind this step's record (chs_tail.h: cs_next)
-    fires = (cs_next > 500 && (cs_next % 2) == 0);
-  }
   if (E->csHost >= 0) E->csHost += 1;                 // (a halted run issues no-ops; the call's end sets the true value)
-  if (last && E->keepResident) {
-    // the last step of the call leaves the field in HBM like ROW_INV_DIAG, and with it what the first column
-    // pass of a following call needs (T1, sum(mu^2)): that call then starts without an entry pass (run_steps)
-    const bool store = E->storeU;
-    E->storeU = true;
-    rc = P->row_inv(E, ROW_INV_FUSED, T2, E->dU, E->dT1);
-    E->storeU = store;
-  } else {
-    rc = P->row_inv(E, last ? ROW_INV_DIAG : (fa ? ROW_INV_FUSED_ADAPT : ROW_INV_FUSED), T2, E->dU, E->dT1);
-  }
+  rc = P->row_inv(E, p.row_mode, T2, E->dU, E->dT1, p.store_u);
   chs_slot_end(E, SLOT_INV);
   if (rc) return rc;
-  // A firing step with nothing else armed: the reduction's last block works out the coming step's coefficients itself
-  // (k_colmin_slices, `decide`), so the next k_col needs no gate either -- its tiles read them from the state as ever
-  const bool lam_by_colmin = !last && fa && fires && E->csHost >= 0 && E->adaptSparse && E->lamByColmin && E->dc.full_sim &&
-                             !(E->dc.time_limit_s > 0.0) && !E->timer.on;
-  if (!last && E->dc.adaptive_time && (fires || !fa)) {
-    // column sums of the adaptive-step integrand of the NEXT step (solver.py:183); the record of
-    // this step has not advanced computed_steps yet, hence the offset
-    if ((rc = fa ? chs_launch_colmin_rows(E, 1, lam_by_colmin) : chs_launch_mu_colsums(E, 1))) return rc;
-  }
-  // Stop rules armed (energy rule, time limit) or an adaptive time step: the bookkeeping still rides in the
-  // next k_col, whose other workgroups wait for its decision in front of their first global write (gated
-  // tail, gate_wait) -- no 14 us one-block launch per step.  A run being profiled keeps the separate launch.
-  const bool gate = !defer && !E->timer.on && E->partSet[0][0] != nullptr;
-  if (last || (!defer && !gate)) return chs_launch_step_tail(E, last ? 0 : 1);
-  // (an adaptive step whose rule does not fire decides nothing the next k_col needs, unless a stop rule is armed)
-  const bool quiet = (!fires || lam_by_colmin) && fa && E->dc.full_sim && !(E->dc.time_limit_s > 0.0);
-  E->tailDeferred = true;
-  E->tailGated = gate && !quiet;
-  // ... and one whose rule does fire, with nothing else armed, lets the tiles have their coefficients early (chs_tail.h)
-  E->tailEarly = E->tailGated && fires && fa && E->dc.full_sim && !(E->dc.time_limit_s > 0.0) && E->csHost >= 0 && E->adaptSparse && E->gateEarly;
-  E->tailSet = E->parity;
+  if (p.reduce == REDUCE_COLMIN && (rc = chs_launch_colmin_rows(E, 1, p.decide))) return rc;
+  if (p.reduce == REDUCE_SWEEP && (rc = chs_launch_mu_colsums(E, 1))) return rc;
+  if (p.tail_now) return chs_launch_step_tail(E, p.do_pre);
+  E->pending = p.next;
+  E->pending.set = E->parity;
   E->parity ^= 1;
   return CHS_OK;
 }
@@ -378,11 +298,11 @@ int chs_fast_step_unfused(Engine* E) {
   }
   if ((rc = chs_launch_pre(E))) return rc;
   chs_slot_begin(E, SLOT_SPEC);
-  rc = P->col(E, MODE_STEP, E->dT1, E->dT2, E->dHat, nullptr);
+  rc = P->col(E, MODE_STEP, E->dT1, E->dT2, E->dHat, nullptr, no_rider());
   chs_slot_end(E, SLOT_SPEC);
   if (rc) return rc;
   chs_slot_begin(E, SLOT_INV);
-  rc = P->row_inv(E, ROW_INV_PLAIN, E->dT2, E->dU, nullptr);
+  rc = P->row_inv(E, ROW_INV_PLAIN, E->dT2, E->dU, nullptr, 1);
   chs_slot_end(E, SLOT_INV);
   return rc;
 }

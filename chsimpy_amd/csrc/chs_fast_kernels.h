@@ -1352,7 +1352,6 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_col(const typename C::T*
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-enum { ROW_INV_PLAIN = 0, ROW_INV_DIAG = 1, ROW_INV_FUSED = 2, ROW_INV_FUSED_ADAPT = 3 };
 enum { ROW_FWD_PLAIN = 0, ROW_FWD_POINTWISE = 1 };
 
 struct FastPlan {
@@ -1361,8 +1360,10 @@ struct FastPlan {
   size_t off_tw0, off_twa, off_twb, off_wp, off_t1, off_t2, off_lam4 = 0, off_sin4 = 0;  // element offsets
   int (*row_fwd)(Engine*, const void*, void*, int) = nullptr;   // mode: ROW_FWD_PLAIN / _POINTWISE
   int (*row_fwd2)(Engine*, const void*, void*, void*) = nullptr;
-  int (*row_inv)(Engine*, int, const void*, void*, void*) = nullptr;
-  int (*col)(Engine*, int, const void*, void*, void*, void*) = nullptr;
+  // mode: ROW_INV_* (chs_step_host.h); store_u: the fused kernels write the whole field (the others always do)
+  int (*row_inv)(Engine*, int mode, const void* t2, void* u, void* t1, int store_u) = nullptr;
+  // rider: what k_col<MODE_STEP> carries as its extra workgroup (the other modes carry nothing)
+  int (*col)(Engine*, int mode, const void* tin, void* tout, void* hat, void* nat, const ColRider& rider) = nullptr;
   int (*init)(Engine*) = nullptr;
   // batched step kernels (N <= 2048; nullptr where no batch is offered): E0 = any member (tables, lambda),
   // `mem` = the device array of the B member records
@@ -1438,7 +1439,7 @@ struct Launch {
     CHS_HIP(hipGetLastError());
     return CHS_OK;
   }
-  static int row_inv(Engine* E, int mode, const void* t2, void* u, void* t1) {
+  static int row_inv(Engine* E, int mode, const void* t2, void* u, void* t1, int store_u) {
     const int grid = C::N / C::C;
     const FTables<T> tb = get_tables<T>(E);
     if (mode == ROW_INV_PLAIN)
@@ -1449,37 +1450,36 @@ struct Launch {
                                                                    E->dPartDiag, E->dPartMu, E->dPartRa, 1);
     else if (mode == ROW_INV_FUSED)
       k_row_inv<C, true, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)t2, (T*)u, (T*)t1, tb, E->dc, E->dState,
-                                                                  E->dPartDiag, E->dPartMu, E->dPartRa, E->storeU ? 1 : 0);
+                                                                  E->dPartDiag, E->dPartMu, E->dPartRa, store_u);
     else {
       if constexpr (ADAPT_OK)
         k_row_inv<C, true, true, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)t2, (T*)u, (T*)t1, tb, E->dc, E->dState,
-                                                                          E->dPartDiag, E->dPartMu, E->dPartRa, E->storeU ? 1 : 0, (T*)E->dPartColRows);
+                                                                          E->dPartDiag, E->dPartMu, E->dPartRa, store_u, (T*)E->dPartColRows);
       else { chs_set_error("fused adaptive row kernel is not built for this configuration"); return CHS_EINVAL; }
     }
     CHS_HIP(hipGetLastError());
     return CHS_OK;
   }
-  static int col(Engine* E, int mode, const void* tin, void* tout, void* hat, void* nat) {
+  static int col(Engine* E, int mode, const void* tin, void* tout, void* hat, void* nat, const ColRider& rider) {
     const int grid = CC::N / CC::C;
     const FTables<T> tb = get_tables<T>(E);
     TailArgs ta;
     switch (mode) {
       case MODE_STEP: {
         int g = grid;
-        if (E->tailDeferred) {
-          ta = chs_tail_args(E, E->tailSet, 1);
+        if (rider.tail.any) {
+          ta = chs_tail_args(E, rider.tail.set, 1);
           g = grid + 1;
-          if (E->tailGated) {
+          if (rider.tail.gated) {
             ta.gate = 1; ta.seq = ++E->gateSeq;
             if (E->testGateWithhold) { ta.withhold = 1; ta.gate_spins = 1 << 10; }
-            ta.early = E->tailEarly ? 1 : 0;
+            ta.early = rider.tail.early ? 1 : 0;
           }
-        } else if (E->preRider) {
+        } else if (rider.pre_only) {
           ta = chs_tail_args(E, -1, 1);
           ta.pre_only = 1;
           g = grid + 1;
         }
-        E->preRider = false;
         ta.reverse = (E->stepCount & 1) ? 1 : 0;
         ++E->stepCount;
         k_col<CC, MODE_STEP><<<g, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
