@@ -134,17 +134,50 @@ __device__ __forceinline__ V mul_w16(V a) {
   }
 }
 
-// (a, b) <- (a + w b, a - w b) for a pure 16th root w = exp(-2 pi i ROT/16) in {1, -i, -1, +i}: the rotation
-// is folded into the two additions
+// (a, b) <- (a + w b, a - w b) for a 16th root w = exp(-2 pi i ROT/16) whose components have equal magnitude:
+//   pure (ROT % 4 == 0: 1, -i, -1, +i): the rotation is folded into the two additions;
+//   odd eighth roots (ROT % 4 == 2: sqrt(1/2) (+-1 -+ i)): with (u, v) = (br + bi, bi - br) -- one complex addition --
+//   w b is sqrt(1/2) times (u, v), (v, -u), (-u, -v) or (-v, u), and each result is ONE fused multiply-add on a:
+//   three complex instructions instead of the four of a product followed by a butterfly.
 template <class V, int ROT>
 __device__ __forceinline__ void bfly2_rot(V& a, V& b) {
-  static_assert(ROT % 4 == 0, "pure rotations only");
+  static_assert(ROT % 2 == 0, "roots of equal-magnitude components only");
   constexpr int r = ((ROT % 16) + 16) % 16;
   const V x = a, y = b;
   if constexpr (r == 0) { a = cx_add(x, y); b = cx_sub(x, y); }
   else if constexpr (r == 4) { a = cx_add_mi(x, y); b = cx_add_pi(x, y); }
   else if constexpr (r == 8) { a = cx_sub(x, y); b = cx_add(x, y); }
-  else { a = cx_add_pi(x, y); b = cx_add_mi(x, y); }
+  else if constexpr (r == 12) { a = cx_add_pi(x, y); b = cx_add_mi(x, y); }
+  else {
+    using S = decltype(cx_re(a));
+    const V k = cx_make((S)FC_SQRT1_2, (S)FC_SQRT1_2);
+    const V uv = cx_add_mi(y, y);  // (yr + yi, yi - yr)
+    //                                 S0 H0 S1 H1 NL0 NH0 NL1 NH1
+    if constexpr (r == 2)       { a = pk_fma_k<0, 1, 0, 1, 0, 0, 0, 0>(uv, k, x); b = pk_fma_k<0, 1, 0, 1, 1, 1, 0, 0>(uv, k, x); }
+    else if constexpr (r == 6)  { a = pk_fma_k<1, 0, 0, 1, 0, 1, 0, 0>(uv, k, x); b = pk_fma_k<1, 0, 0, 1, 1, 0, 0, 0>(uv, k, x); }
+    else if constexpr (r == 10) { a = pk_fma_k<0, 1, 0, 1, 1, 1, 0, 0>(uv, k, x); b = pk_fma_k<0, 1, 0, 1, 0, 0, 0, 0>(uv, k, x); }
+    else                        { a = pk_fma_k<1, 0, 0, 1, 1, 0, 0, 0>(uv, k, x); b = pk_fma_k<1, 0, 0, 1, 0, 1, 0, 0>(uv, k, x); }
+  }
+}
+
+// DFT of size 4 on y[0..4) whose operands y[1], y[2], y[3] still await the rotations exp(-2 pi i Rn/16) (the twiddles
+// between the two stages of a radix-16 butterfly).  A rotation of equal-magnitude components that meets a radix-2
+// stage is folded into it (bfly2_rot): R2 into the first stage; R1 and R3 = R1 + 4 (mod 16) -- the same root up to
+// -i -- into the first stage as that -i and into the second as their common root.  The others (the cos pi/8 roots) are
+// multiplied out.  ROTI = the second stage's own rotation of its odd pair: 4 (-i) forward, 12 (+i) inverse.
+template <class V, int R1, int R2, int R3, int ROTI>
+__device__ __forceinline__ void dft4_rot(V* y) {
+  constexpr bool F2 = (R2 % 2) == 0;
+  constexpr bool F13 = (R1 % 4) == 2 && ((R3 - R1) % 16 + 16) % 4 == 0;
+  V t0 = y[0], t1 = y[2], t2 = y[1], t3 = y[3];
+  if constexpr (F2) bfly2_rot<V, R2>(t0, t1);
+  else { t1 = mul_w16<V, R2, false>(t1); bfly2_rot<V, 0>(t0, t1); }
+  if constexpr (F13) bfly2_rot<V, R3 - R1>(t2, t3);
+  else { t2 = mul_w16<V, R1, false>(t2); t3 = mul_w16<V, R3, false>(t3); bfly2_rot<V, 0>(t2, t3); }
+  constexpr int P = F13 ? R1 : 0;
+  bfly2_rot<V, P>(t0, t2);
+  bfly2_rot<V, P + ROTI>(t1, t3);
+  y[0] = t0; y[2] = t2; y[1] = t1; y[3] = t3;
 }
 
 // In-place DFT of size R on z[0..R): y[k] = sum_j a[j] exp(-+2 pi i jk/R)
@@ -182,35 +215,31 @@ struct Dft {
   static_assert(R == 8 || R == 16, "radix must be 2, 4, 8 or 16");
   template <int N2, int K1>
   static constexpr int tw_idx() { return (N2 * K1 * 16) / R; }
-  // the twiddle between the two stages; B == 2: a pure rotation is left to the second stage (bfly2_rot)
+  // the root of the twiddle between the two stages, conjugation resolved
   template <int N2, int K1>
-  static __device__ __forceinline__ V tw(V a) {
-    if constexpr (B == 2 && W16<tw_idx<N2, K1>(), INV>::pure) return a;
-    else return mul_w16<V, tw_idx<N2, K1>(), INV>(a);
-  }
+  static constexpr int rot() { return W16<tw_idx<N2, K1>(), INV>::idx; }
+  // The twiddles are applied by the second stage: folded into its additions where the root allows it (bfly2_rot,
+  // dft4_rot), multiplied out there otherwise.
   template <int N2>
   static __device__ __forceinline__ void col(const V* z, V (*c)[A]) {
     V x[A];
 #pragma unroll
     for (int n1 = 0; n1 < A; ++n1) x[n1] = z[B * n1 + N2];
     Dft<V, A, INV>::run(x);
-    c[N2][0] = x[0];
-    c[N2][1] = tw<N2, 1>(x[1]);
-    c[N2][2] = tw<N2, 2>(x[2]);
-    c[N2][3] = tw<N2, 3>(x[3]);
+#pragma unroll
+    for (int k1 = 0; k1 < A; ++k1) c[N2][k1] = x[k1];
   }
   template <int K1>
   static __device__ __forceinline__ void row(V* z, V (*c)[A]) {
     if constexpr (B == 2) {
       V y0 = c[0][K1], y1 = c[1][K1];
-      constexpr int rot = W16<tw_idx<1, K1>(), INV>::pure ? W16<tw_idx<1, K1>(), INV>::idx : 0;
-      bfly2_rot<V, rot>(y0, y1);
+      bfly2_rot<V, rot<1, K1>()>(y0, y1);
       z[K1] = y0; z[K1 + A] = y1;
     } else {
       V y[B];
 #pragma unroll
       for (int n2 = 0; n2 < B; ++n2) y[n2] = c[n2][K1];
-      Dft<V, B, INV>::run(y);
+      dft4_rot<V, rot<1, K1>(), rot<2, K1>(), rot<3, K1>(), INV ? 12 : 4>(y);
 #pragma unroll
       for (int k2 = 0; k2 < B; ++k2) z[K1 + A * k2] = y[k2];
     }

@@ -417,6 +417,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd(const typename C
   typename C::V z[C::E];
   double s2 = 0.0;
   const T RT = (T)dc.RT, BRT = (T)dc.BRT, A0 = (T)dc.A0, A1 = (T)dc.A1;
+  [[maybe_unused]] const PwConsts pwk = chs_pw_consts(dc.RT, dc.B, dc.BRT, dc.A0, dc.A1);  // (fp64: chs_energy_mu_from_logs)
   const unsigned urow = (unsigned)row * C::N;  // (32-bit offsets from the uniform base, see slot_boff)
 #pragma unroll
   for (int q = 0; q < C::NP0; ++q) {
@@ -443,7 +444,9 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd(const typename C
     auto mu = [&](T& u) {
       const T uinv = T(1) - u;
       const T lU = chs_log_unit_tab<T>(u, ltab, dom), lV = chs_log_unit_tab<T>(uinv, ltab, dom);
-      const T m = chs_mu_from_logs_fast<T>(u, uinv, lU, lV, RT, BRT, A0, A1);
+      T m;
+      if constexpr (sizeof(T) == 8) { T e; chs_energy_mu_from_logs<false, true>(u, uinv, lU, lV, pwk, e, m); }
+      else m = chs_mu_from_logs_fast<T>(u, uinv, lU, lV, RT, BRT, A0, A1);
       s2 += (double)m * (double)m;
       u = m;
       asm volatile("" : "+v"(u), "+v"(s2), "+v"(dom));  // one grid point at a time (register pressure)
@@ -455,7 +458,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd(const typename C
       z[e] = cx_make(a, b);
       __builtin_amdgcn_sched_barrier(0);   // (as in the fused row kernel: one value pair at a time)
     }
-    if (dom > (unsigned)(CHS_LOGTAB_N - 1)) s2 = __builtin_nan("");  // U left (0,1): L2 of this step becomes NaN
+    if (chs_log_dom_bad(dom)) s2 = __builtin_nan("");  // U left (0,1): L2 of this step becomes NaN
     // (the wavefront sums go to LDS here: no register carries the sum across the transform)
     const double acc1[1] = {s2};
     block_reduce_begin<1, FreshLane<C>::value>(acc1, red, wv);
@@ -512,6 +515,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
   if constexpr (sizeof(T) == 8 || RTWM != 0) __syncthreads();  // the log table and the twiddles are visible
   typename C::V z[C::E];
   const T RT = (T)dc.RT, BRT = (T)dc.BRT, A0 = (T)dc.A0, A1 = (T)dc.A1;
+  [[maybe_unused]] const PwConsts pwk = chs_pw_consts(dc.RT, dc.B, dc.BRT, dc.A0, dc.A1);  // (fp64: chs_energy_mu_from_logs)
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     const int lp = row_l<C, true>(wv, l);
@@ -540,7 +544,9 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
       auto mu = [&](T& u) {
         const T uinv = T(1) - u;
         const T lU = chs_log_unit_tab<T>(u, ltab, dom), lV = chs_log_unit_tab<T>(uinv, ltab, dom);
-        const T m = chs_mu_from_logs_fast<T>(u, uinv, lU, lV, RT, BRT, A0, A1);
+        T m;
+        if constexpr (sizeof(T) == 8) { T e; chs_energy_mu_from_logs<false, true>(u, uinv, lU, lV, pwk, e, m); }
+        else m = chs_mu_from_logs_fast<T>(u, uinv, lU, lV, RT, BRT, A0, A1);
         s2 += (double)m * (double)m;
         u = m;
         asm volatile("" : "+v"(u), "+v"(s2), "+v"(dom));  // one grid point at a time (register pressure)
@@ -551,7 +557,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_fwd2(const typename 
         mu(a); mu(b);
         z[e] = cx_make(a, b);
       }
-      if (dom > (unsigned)(CHS_LOGTAB_N - 1)) s2 = __builtin_nan("");  // U left (0,1): L2 of the first step becomes NaN
+      if (chs_log_dom_bad(dom)) s2 = __builtin_nan("");  // U left (0,1): L2 of the first step becomes NaN
       const double acc1[1] = {s2};
       block_reduce_begin<1, true>(acc1, red, wv);
     }
@@ -749,14 +755,22 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
     // assertion, timedata.py:10): the table index of the logs doubles as the check (chs_log_unit_tab),
     // one integer maximum per log; the sums are poisoned at the end.
     unsigned dom = 0;
+    // (fp64: energy density and EnergieEut from shared products, chs_energy_mu_from_logs; the fp32 engine keeps the
+    // two separate expressions, which its compiler output packs)
+    [[maybe_unused]] const PwConsts pwk = chs_pw_consts(dc.RT, dc.B, dc.BRT, dc.A0, dc.A1);
     auto point = [&](T& u) {
       const T uinv = T(1) - u;
       const T lU = chs_log_unit_tab<T>(u, ltab, dom), lV = chs_log_unit_tab<T>(uinv, ltab, dom);
-      sE += (double)chs_energy_from_logs_fast<T>(u, uinv, lU, lV, RT, B, A0, A1);
+      [[maybe_unused]] T m = T(0);
+      if constexpr (sizeof(T) == 8) {
+        chs_energy_mu_from_logs<true, FUSE>(u, uinv, lU, lV, pwk, sE, m);
+      } else {
+        sE += (double)chs_energy_from_logs_fast<T>(u, uinv, lU, lV, RT, B, A0, A1);
+        if constexpr (FUSE) m = chs_mu_from_logs_fast<T>(u, uinv, lU, lV, RT, BRT, A0, A1);
+      }
       sPS += fabs((double)u - mean);
       cSA += ((double)u < thr) ? 1 : 0;
       if constexpr (FUSE) {
-        const T m = chs_mu_from_logs_fast<T>(u, uinv, lU, lV, RT, BRT, A0, A1);
         s2 += (double)m * (double)m;
         u = m;
         // opaque use: finishes this grid point before the next one starts, so the
@@ -775,7 +789,7 @@ __global__ __launch_bounds__(C::THREADS, C::WPS) void k_row_inv(const typename C
       z[e] = cx_make(a, b);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (dom > (unsigned)(CHS_LOGTAB_N - 1)) sE = __builtin_nan("");  // U left (0,1): the record of this step becomes NaN
+    if (chs_log_dom_bad(dom)) sE = __builtin_nan("");  // U left (0,1): the record of this step becomes NaN
     // The five sums leave the registers HERE (wavefront sums into `red`), not at the end of the kernel: carried across the
     // forward transform they were what the register allocator spilled (and a spill reload waits behind every T1 store).
     const double acc[5] = {sE, sEdge, sPS, (double)cSA, s2};

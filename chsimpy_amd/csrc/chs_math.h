@@ -112,38 +112,42 @@ __device__ __forceinline__ double chs_log_ratio_f64(double a, double b) {
 }
 
 // Table-driven log for the fused row kernel's pointwise part (no division, no domain selects):
-//   x = 2^e m, m in [1/2, 1) (frexp);  i = rint(256 m) in [128, 256];  r = fma(m, rc_i, -1) with
-//   rc_i = fl(256/i) from the table (|r| <= 1/256);  log x = (e ln2 + lc_i) + log1p(r), lc_i = fl(-log rc_i),
-//   log1p by its series to r^6 (truncation r^7/7 < 2e-18).  `tab` = chs_log_table copied to LDS.
-// 13 floating-point + 3 integer instructions and one LDS read.
+//   x = 2^e m, m in [1/2, 1) (frexp);  i = floor(256 m + 1/2) in [128, 256], read off the high word of m by integer
+//   arithmetic (its 20 mantissa bits count the interval in steps of 2^-21; the low word cannot change the floor);
+//   r = fma(m, rc_i, -1) with rc_i = fl(256/i) from the table (|r| <= 1/256);
+//   log x = (e ln2 + lc_i) + log1p(r), lc_i = fl(-log rc_i), log1p(r) = r q(r) by its series to r^6 (truncation
+//   r^7/7 < 2e-18) as one Horner chain that ends in the sum.  `tab` = chs_log_table copied to LDS.
+// 11 floating-point + 4 integer instructions and one LDS read.
 // Accuracy: for 0 < x <= 1 -- all the timestep ever asks for: x = U or 1-U -- every term has the same
 // sign (e <= 0, lc_i <= 0) and the result is within 2.5 ulp (tests/test_gpu_math.py); x -> 1 gives
 // e = 0, i = 256, lc = 0: log x = log1p(r) with r = x - 1 exactly.  For x > 1 the terms e ln2 > 0 and
 // lc_i < 0 cancel: the ABSOLUTE error stays ~2e-16 max(1, |log x|) but the relative error grows as
 // log x -> 0+; ln2 is a single constant (no hi/lo split) because of that sign structure.
-// Domain: the index doubles as the domain check.  For finite x > 0 it lies in [128, 256]; x <= 0 gives
-// m <= 0 and an index below 128 (-> huge as unsigned), which `domain` (a running unsigned maximum of
-// i - 128, to be compared with 128 once per row) records: the caller turns the sums into NaN then,
-// like numpy's log of a non-positive number does for the reference (timedata.py:10).  NaN and +inf
-// propagate through r.
+// Domain: the index word doubles as the domain check.  w = hi(m) - hi(1/2) + rounding is at most CHS_LOG_DOM_MAX for
+// every finite x > 0 (denormals included: frexp normalises them); x <= 0 gives m <= 0, NaN and inf stay what they
+// are, and all of those make w larger (as unsigned).  `domain` is the running unsigned maximum of w, to be tested
+// once per row with chs_log_dom_bad: the caller turns the sums into NaN then, like numpy's log of a non-positive
+// number does for the reference (timedata.py:10).  NaN and +inf also propagate through r.
 #include "chs_log_table.h"
 #define CHS_LN2 0.6931471805599453
+#define CHS_LOG_DOM_MAX 0x100FFFu  /* 20 mantissa bits + the rounding term 2^12 */
+__device__ __forceinline__ bool chs_log_dom_bad(unsigned domain) { return domain > CHS_LOG_DOM_MAX; }
 __device__ __forceinline__ double chs_log_unit_tab_f64(double x, const double2* tab, unsigned& domain) {
 #pragma clang fp contract(off)
   const double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
   const int e = __builtin_amdgcn_frexp_exp(x);
-  const double u = __builtin_fma(m, 256.0, 0x1.8p52);  // the low word of 1.5*2^52 + n is n
-  const unsigned i = (unsigned)(__double2loint(u) - CHS_LOGTAB_I0);
-  domain = max(domain, i);
-  const double2 t = tab[min(i, (unsigned)(CHS_LOGTAB_N - 1))];
+  const unsigned w = (unsigned)__double2hiint(m) - (0x3FE00000u - 0x1000u);
+  domain = max(domain, w);
+  const double2 t = tab[min(w, CHS_LOG_DOM_MAX) >> 13];  // i - 128 <= CHS_LOGTAB_N - 1
   const double r = __builtin_fma(m, t.x, -1.0);
   double p = __builtin_fma(r, -1.0 / 6.0, 1.0 / 5.0);
   p = __builtin_fma(r, p, -1.0 / 4.0);
   p = __builtin_fma(r, p, 1.0 / 3.0);
   p = __builtin_fma(r, p, -0.5);
-  const double lp = __builtin_fma(r * r, p, r);
-  return __builtin_fma((double)e, CHS_LN2, t.y) + lp;
+  const double q = __builtin_fma(r, p, 1.0);
+  return __builtin_fma(r, q, __builtin_fma((double)e, CHS_LN2, t.y));
 }
+static_assert((CHS_LOG_DOM_MAX >> 13) == CHS_LOGTAB_N - 1, "the clamped index is the table's last entry");
 
 // fp32 engine: x = U, 1-U or their quotient, never denormal: the hardware log2 (1 ulp) times ln 2 instead of the
 // library's range-checked sequence (~10 instructions per logarithm); log of a non-positive number gives NaN / -inf
@@ -233,6 +237,42 @@ __device__ __forceinline__ T chs_mu_from_logs_fast(T U, T Uinv, T lU, T lV, T RT
   const T t2 = (A0 + A1 * U2inv) * U2inv;
   const T t3 = ((T(2) * A1) * U) * Uinv;
   return ((t1 - BRT) + t2) - t3;
+}
+
+// fp64 row kernels: the energy density and EnergieEut of one grid point from SHARED intermediates, every multiply-add
+// an explicit fma.  With Uinv = 1 - U the two expressions above are, exactly,
+//   E  = RT (lV + U d) + U (g Uinv - RT B)          d = lU - lV,  V2 = Uinv - U,  g = A0 + A1 V2
+//   mu = RT d + V2 (A0 + 3/2 A1 V2) - (BRT + A1/2)  (U Uinv = (1 - V2^2)/4)
+// (U lU + Uinv lV = lV + U d; near U -> 1 its terms cancel like those of the literal form do, and the absolute
+// error stays a few ulp of max |log|: it is the SUM over the grid that is recorded.)
+// E is added to the running sum `sE` by two fmas instead of being formed first.  ENERGY costs 7 instructions, MU 5,
+// both together 10 (V2 and d are shared).  PwConsts holds the uniform constants in the form the fmas want, formed
+// once per kernel.
+struct PwConsts {
+  double RT, A0, A1, A1h, nRTB, c0;  // A1h = 3/2 A1, nRTB = -RT B, c0 = -(BRT + A1/2)
+};
+__device__ __forceinline__ PwConsts chs_pw_consts(double RT, double B, double BRT, double A0, double A1) {
+  PwConsts k;
+  k.RT = RT; k.A0 = A0; k.A1 = A1; k.A1h = 1.5 * A1; k.nRTB = -(RT * B); k.c0 = -(BRT + 0.5 * A1);
+  return k;
+}
+template <bool ENERGY, bool MU>
+__device__ __forceinline__ void chs_energy_mu_from_logs(double U, double Uinv, double lU, double lV, const PwConsts& k,
+                                                        double& sE, double& mu) {
+  const double V2 = Uinv - U;
+  const double d = lU - lV;
+  if constexpr (ENERGY) {
+    const double g = __builtin_fma(k.A1, V2, k.A0);
+    const double t = __builtin_fma(g, Uinv, k.nRTB);
+    const double s = __builtin_fma(U, d, lV);
+    sE = __builtin_fma(k.RT, s, sE);
+    sE = __builtin_fma(U, t, sE);
+  }
+  if constexpr (MU) {
+    const double h = __builtin_fma(k.A1h, V2, k.A0);
+    const double m = __builtin_fma(k.RT, d, k.c0);
+    mu = __builtin_fma(V2, h, m);
+  }
 }
 
 // Adaptive-step integrand, chsimpy/solver.py:182-183:

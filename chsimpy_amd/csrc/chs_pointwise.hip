@@ -227,7 +227,7 @@ __global__ __launch_bounds__(PW_THREADS) void k_diag(const T* __restrict__ U, De
       up = cur; cur = nxt;
     }
   }
-  if (dom > (unsigned)(CHS_LOGTAB_N - 1)) sE = __builtin_nan("");  // U left (0,1): the logarithms are undefined
+  if (chs_log_dom_bad(dom)) sE = __builtin_nan("");  // U left (0,1): the logarithms are undefined
   const double tE = block_sum(sE, scratch);
   const double tG = block_sum(sG, scratch);
   const double tP = block_sum(sPS, scratch);
@@ -910,7 +910,7 @@ __global__ void k_test_math(int which, const double* __restrict__ a, const doubl
   if (i >= n) return;
   double r;
   unsigned dom = 0;
-  if (which == 5) { r = chs_log_unit_tab_f64(a[i], ltab, dom); if (dom > (unsigned)(CHS_LOGTAB_N - 1)) r = __builtin_nan(""); }
+  if (which == 5) { r = chs_log_unit_tab_f64(a[i], ltab, dom); if (chs_log_dom_bad(dom)) r = __builtin_nan(""); }
   else if (which == 0) r = chs_log_f64(a[i]);
   else if (which == 1) r = chs_log_ratio_f64(a[i], b[i]);
   else if (which == 4) r = chs_log_pos_f64(a[i]);
