@@ -21,6 +21,7 @@ CHS_STEP_REDERIVE_HAT = 2
 CHS_STEP_LAST_CALL = 4
 CHS_STEP_KEEP_T1 = 8
 CHS_NKERNELS = 8
+CHS_MORPH_WORDS = 7           # int64 words of chs_morphology: Q0, Q1, Q2, QD, Q3, Q4, border
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -37,6 +38,7 @@ SYMBOLS = (
     'chs_batch_prepare', 'chs_batch_step_n', 'chs_batch_get_state', 'chs_batch_set_state',
     'chs_batch_step_n_queued', 'chs_batch_member_rows', 'chs_batch_engine',
     'chs_structure_factor_bins', 'chs_structure_factor', 'chs_structure_factor_last_ms', 'chs_batch_structure_factor',
+    'chs_morphology', 'chs_morphology_last_ms', 'chs_batch_morphology',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -157,6 +159,9 @@ def load():
     lib.chs_structure_factor.argtypes = [vp, dp, C.c_int32]
     lib.chs_structure_factor_last_ms.argtypes = [vp, dp]
     lib.chs_batch_structure_factor.argtypes = [vp, C.c_int32, dp, C.c_int32]
+    lib.chs_morphology.argtypes = [vp, C.c_double, i64p]
+    lib.chs_morphology_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_morphology.argtypes = [vp, C.c_int32, dp, i64p]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -176,6 +181,10 @@ def pool_count():
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _i64ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
 def _as_f64(a, shape=None):
@@ -315,6 +324,19 @@ class Engine:
         self._check(self.lib.chs_structure_factor_last_ms(self._h, _dptr(ms)), 'chs_structure_factor_last_ms')
         return ms
 
+    def morphology(self, threshold):
+        """The seven int64 words Q0, Q1, Q2, QD, Q3, Q4, border of the field the device holds at `threshold`
+        (chs_morphology; chsimpy_amd/morphology.py derives the rest)."""
+        out = np.empty(CHS_MORPH_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_morphology(self._h, float(threshold), _i64ptr(out)), 'chs_morphology')
+        return out
+
+    def morphology_ms(self):
+        """Device time (ms) of the last `morphology`."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.chs_morphology_last_ms(self._h, C.byref(ms)), 'chs_morphology_last_ms')
+        return float(ms.value)
+
     @property
     def engine(self):
         return {CHS_ENGINE_DIRECT: 'direct', CHS_ENGINE_FAST: 'fast', CHS_ENGINE_CHIRP: 'chirp'}[self.lib.chs_engine(self._h)]
@@ -438,6 +460,15 @@ class Batch:
         self._check(self.lib.chs_batch_structure_factor(self._h, -1 if member is None else int(member), _dptr(ssum), nb),
                     'chs_batch_structure_factor')
         return ssum
+
+    def morphology(self, thresholds, member=None):
+        """The seven words of one member at the threshold `thresholds` ([7]), or of all members in one device pass at
+        their thresholds `thresholds[B]` ([B, 7]) for member=None (chs_batch_morphology with member = -1)."""
+        t = _as_f64(np.atleast_1d(thresholds), (1,) if member is not None else (self.B,))
+        out = np.empty(CHS_MORPH_WORDS if member is not None else (self.B, CHS_MORPH_WORDS), dtype=np.int64)
+        self._check(self.lib.chs_batch_morphology(self._h, -1 if member is None else int(member), _dptr(t), _i64ptr(out)),
+                    'chs_batch_morphology')
+        return out
 
     def get_state(self, member):
         s = chs_state()

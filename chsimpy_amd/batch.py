@@ -121,6 +121,9 @@ class _Member:
     def set_U(self, U):
         self._b.set_U(self._m, U)
 
+    def morphology(self, threshold):
+        return self._b.morphology(threshold, self._m)
+
     def close(self):
         pass  # (the batch owns the device state)
 
@@ -246,6 +249,28 @@ class BatchSolver:
             return spectrum.StructureFactor(b.structure_factor(member), s.params.N, s.solution.delx)
         ssum = b.structure_factor()
         return [spectrum.StructureFactor(ssum[m], s.params.N, s.solution.delx) for m, s in enumerate(self.solvers)]
+
+    def morphology(self, member=None, threshold=None):
+        """The members' morphology (`Solver.morphology`): a list of one `morphology.Morphology` per member from one
+        device pass over the batch, or the one of ``member``.  ``threshold``: one value for all, one per member, or None
+        for every member's own ``params.threshold``.  The members' runs do not notice the look."""
+        from . import morphology
+        b = self._get_batch()
+        for s in self.solvers:
+            s._push_edited_U()
+        if threshold is None:
+            ts = [float(s.params.threshold) for s in self.solvers]
+        elif np.ndim(threshold) == 0:
+            ts = [float(threshold)] * len(self.solvers)
+        else:
+            ts = [float(t) for t in threshold]
+            if len(ts) != len(self.solvers):
+                raise ValueError(f"{len(self.solvers)} thresholds are needed, got {len(ts)}")
+        if member is not None:
+            s = self.solvers[member]
+            return morphology.Morphology(b.morphology(ts[member], member), s.params.N, ts[member], s.solution.delx)
+        words = b.morphology(ts)
+        return [morphology.Morphology(words[m], s.params.N, ts[m], s.solution.delx) for m, s in enumerate(self.solvers)]
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

@@ -161,6 +161,7 @@ struct Batch {
   std::vector<long long> hQueue0;
   std::vector<std::vector<double>> qRows;  // the members' rows of the last queued call (chs_batch_member_rows)
   void* spec = nullptr;          // chs_batch_structure_factor of all members: its buffers (chs_spectrum.hip), at the first call
+  void* morph = nullptr;         // chs_batch_morphology of all members: its buffers (chs_morphology.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -177,6 +178,7 @@ void batch_free(Batch* b) {
     chs_destroy((chs_handle)b->m[i]);
   }
   chs_spectrum_free(&b->spec);
+  chs_morph_free(&b->morph);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -786,4 +788,13 @@ extern "C" int chs_batch_structure_factor(chs_batch h, int32_t member, double* s
   if (member < -1 || member >= b->B) return bad("chs_batch_structure_factor: no such member");
   if (member >= 0) return chs_spectrum_one(b->m[(size_t)member], ssum, nbins, "chs_batch_structure_factor");
   return chs_spectrum_all(b->m.data(), b->B, b->stream, b->chirp, &b->spec, ssum, nbins, "chs_batch_structure_factor");
+}
+
+// The morphology of one member -- the single handle's look on the batch's stream -- or of all of them at once.
+extern "C" int chs_batch_morphology(chs_batch h, int32_t member, const double* threshold, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_morphology: null handle");
+  if (member < -1 || member >= b->B) return bad("chs_batch_morphology: no such member");
+  if (member >= 0) return chs_morph_one(b->m[(size_t)member], threshold, out, "chs_batch_morphology");
+  return chs_morph_all(b->m.data(), b->B, b->stream, &b->morph, threshold, out, "chs_batch_morphology");
 }

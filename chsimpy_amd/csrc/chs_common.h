@@ -249,6 +249,7 @@ struct Engine {
   void* dTw = nullptr;         // fast engine: twiddle tables
   void* chirp = nullptr;       // chirp engine: its plan and tables (chs_chirp.hip)
   void* spec = nullptr;        // structure factor: partial bins, result, events (chs_spectrum.hip), at the first call
+  void* morph = nullptr;       // morphology: tile partials, result, events (chs_morphology.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -398,3 +399,12 @@ int chs_spectrum_one(Engine* E, double* ssum, int32_t nbins, const char* who);
 // *buf is the batch's own buffer set, allocated here at the first call and freed by chs_spectrum_free
 int chs_spectrum_all(Engine* const* m, int B, hipStream_t s, bool chirp, void** buf, double* ssum, int32_t nbins, const char* who);
 void chs_spectrum_free(void** buf);
+
+// ---- morphology (chs_morphology.hip) ------------------------------------------
+// Bit-quad counts of the thresholded field: out[CHS_MORPH_WORDS] of one handle at *threshold ...
+int chs_morph_one(Engine* E, const double* threshold, int64_t* out, const char* who);
+// ... and out[B][CHS_MORPH_WORDS] of all members of a batch (one stream `s`, one N and element type) at threshold[B], one
+// launch pair; *buf is the batch's own buffer set, allocated here at the first look and freed by chs_morph_free
+int chs_morph_all(Engine* const* m, int B, hipStream_t s, void** buf, const double* threshold, int64_t* out, const char* who);
+void chs_morph_free(void** buf);
+void chs_morph_forget(void* buf);   // the buffers stay, the time of the last look goes

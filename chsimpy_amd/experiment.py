@@ -128,9 +128,17 @@ def _domain_row(sf):
     return (sf.k1, sf.ell, sf.ell_phys)
 
 
-def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None):
+def _morphology_row(mo):
+    """(threshold, n_A, SA, perimeter, perimeter_inner, euler8, euler4) of a member's final field
+    (chsimpy_amd.morphology.Morphology)."""
+    return (mo.threshold, mo.n_A, mo.SA, mo.perimeter, mo.perimeter_inner, mo.euler8, mo.euler4)
+
+
+def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None,
+                       morphology=None):
     """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains`` (a dict): the
-    member's domain size, measured on the device behind its run, goes to ``domains[run_id]``."""
+    member's domain size, measured on the device behind its run, goes to ``domains[run_id]``; ``morphology`` (a dict):
+    likewise the morphology of its final field at ``params.threshold``."""
     from .simulator import Simulator
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
@@ -138,6 +146,8 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
         solution = simulator.solve()
         if domains is not None:
             domains[run_id] = _domain_row(simulator.solver.structure_factor())
+        if morphology is not None:
+            morphology[run_id] = _morphology_row(simulator.solver.morphology())
         simulator.export()
         rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
@@ -146,11 +156,12 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
     return rec
 
 
-def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None):
+def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None,
+                  morphology=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
-    members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``: as in
-    run_experiment_gpu, from one device pass over the group."""
+    members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``,
+    ``morphology``: as in run_experiment_gpu, each from one device pass over the group."""
     from .batch import BatchSolver
     from .simulator import Simulator
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
@@ -161,6 +172,9 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
         if domains is not None:
             for i, sf in zip(run_ids, bs.structure_factor()):
                 domains[i] = _domain_row(sf)
+        if morphology is not None:
+            for i, mo in zip(run_ids, bs.morphology()):
+                morphology[i] = _morphology_row(mo)
         recs = []
         for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
             # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
@@ -216,6 +230,38 @@ def gather_domains(local, nr_items, rank, world, dist=None, device='cpu'):
     return sorted((int(r[0]),) + r[1:] for r in got)
 
 
+MORPHOLOGY_COLS = ('id', 'threshold', 'n_A', 'SA', 'perimeter', 'perimeter_inner', 'euler8', 'euler4')
+
+
+def gather_morphology(local, nr_items, rank, world, dist=None, device='cpu'):
+    """The members' MORPHOLOGY_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the seven
+    values behind the id.  One all_gather of a (ceil(n/world), 8) float64 block per rank, as gather_domains (the counts
+    are integers below 2^53: exact in float64)."""
+    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
+    if world == 1 or dist is None:
+        return rows
+    import torch
+    per = (nr_items + world - 1) // world
+    buf = torch.full((per, len(MORPHOLOGY_COLS)), float('nan'), dtype=torch.float64, device=device)
+    for k, row in enumerate(rows):
+        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
+    out = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(out, buf)
+    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
+    return sorted((int(r[0]),) + r[1:] for r in got)
+
+
+def write_morphology(file_id, rows):
+    """``<file_id>-morphology.csv``: MORPHOLOGY_COLS per member (--morphology), the counts as integers, the two floats
+    written so that they read back exactly."""
+    name = f"{file_id}-morphology.csv"
+    with open(name, 'w') as f:
+        f.write(','.join(MORPHOLOGY_COLS) + "\n")
+        for i, t, n_A, SA, per, per_in, e8, e4 in rows:
+            f.write(f"{int(i)},{float(t)!r},{int(n_A)},{float(SA)!r},{int(per)},{int(per_in)},{int(e8)},{int(e4)}\n")
+    return name
+
+
 def write_domains(file_id, rows):
     """``<file_id>-domains.csv``: ``id, k1, ell, ell_phys`` per member (--domain-size), the floats written so that
     they read back exactly."""
@@ -251,7 +297,7 @@ def write_results(file_id, records):
 
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
-                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None):
+                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None, morphology=None):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -273,9 +319,15 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
 
     ``domains`` (a dict, with the default run functions): every member's domain size -- first moment k1 of the radially
     averaged structure factor of its final field, the characteristic length 2N/k1 and that length in the solver's unit
-    -- is measured on the device behind its run and left in ``domains[run_id]`` for this rank's runs (gather_domains)."""
+    -- is measured on the device behind its run and left in ``domains[run_id]`` for this rank's runs (gather_domains).
+
+    ``morphology`` (a dict, with the default run functions): likewise the morphology of every member's final field at
+    its ``params.threshold`` -- area, interface length, Euler numbers (chsimpy_amd/morphology.py) -- in
+    ``morphology[run_id]`` (gather_morphology)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     dom = {} if domains is None else {'domains': domains}   # (the run functions are called as ever without it)
+    if morphology is not None:
+        dom['morphology'] = morphology
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
             return run_experiment_gpu(run_id, p, rv, al, U_init, **dom)
@@ -367,6 +419,9 @@ def main(argv=None):
                     'arrays from the start)')
     ap.add_argument('--domain-size', action='store_true', help='measure every member\'s domain size on the device behind its '
                     'run (radially averaged structure factor of the final field): <id>-domains.csv with id, k1, ell, ell_phys')
+    ap.add_argument('--morphology', action='store_true', help='measure the morphology of every member\'s final field on the '
+                    'device behind its run (bit-quad counts of the field below the threshold): <id>-morphology.csv with id, '
+                    'threshold, n_A, SA, perimeter, perimeter_inner, euler8, euler4')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
     ap.add_argument('--backend', default=os.environ.get('CHS_DIST_BACKEND', 'nccl'),
@@ -418,15 +473,23 @@ def main(argv=None):
                        + ([f"queue_members, {a.queue_members}"] if (a.batch > 0 and a.queue) else [])
                        + (["dry_run, True"] if a.dry_run else []))
     domains = {} if a.domain_size else None
+    morph = {} if a.morphology else None
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
                            batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
-                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains)
+                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains,
+                           **({} if morph is None else {'morphology': morph}))
     if domains is not None:
         if a.dry_run:   # (members without device work: a function of the run id, as their records are)
             nr = make_rand_values(ep)[2]
             domains = {i: (1.0 + i, 2.0 * p.N / (1.0 + i), 2.0 * p.N / (1.0 + i) * p.L / (p.N - 1)) for i in my_run_ids(nr, rank, world)}
         domain_rows = gather_domains(domains, make_rand_values(ep)[2], rank, world, dist, device)
+    if morph is not None:
+        nr = make_rand_values(ep)[2]
+        if a.dry_run:   # (made up from the run id, as above: a full field with i single-pixel holes)
+            morph = {i: (float(p.threshold), p.N * p.N - i, (p.N * p.N - i) / (p.N * p.N), 4 * p.N + 4 * i, 4 * i, 1 - i, 1 - i)
+                     for i in my_run_ids(nr, rank, world)}
+        morphology_rows = gather_morphology(morph, nr, rank, world, dist, device)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)
@@ -436,6 +499,8 @@ def main(argv=None):
         print(f"  {p.file_id}-results.csv")
         if domains is not None:
             print(f"  {write_domains(p.file_id, domain_rows)}")
+        if morph is not None:
+            print(f"  {write_morphology(p.file_id, morphology_rows)}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, mport, spectrum
+from . import _lib, morphology, mport, spectrum
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -164,6 +164,16 @@ class Solver:
         eng = self._get_engine()
         self._push_edited_U()
         return spectrum.StructureFactor(eng.structure_factor(), self.params.N, self.solution.delx)
+
+    def morphology(self, threshold=None):
+        """Area, interface length and Euler number of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``, the one of the recorded ``SA``): a `morphology.Morphology` from one sweep on the device
+        between two calls, which the run does not notice.  A field the host edited is pushed first, as solve_or_resume
+        does.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        eng = self._get_engine()
+        self._push_edited_U()
+        return morphology.Morphology(eng.morphology(t), self.params.N, t, self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

@@ -252,6 +252,37 @@ int chs_structure_factor(chs_handle h, double* ssum, int32_t nbins);
  * U - mean), ms[1] the transform, ms[2] the binning (both stages).  CHS_ESTATE before the first call. */
 int chs_structure_factor_last_ms(chs_handle h, double ms[3]);
 
+/* ---- Morphology of the thresholded field: area, interface length, Euler number -------------
+ * Foreground: X[i][j] = ((double)U[i][j] < t) for the N x N field U and a finite threshold t -- a strict comparison in
+ * double on the stored element (an fp32 handle's element widened); a NaN pixel and a pixel equal to t are background.
+ * Windows: X padded with one ring of background has (N+1)^2 windows of 2 x 2 pixels; window (i, j), 0 <= i, j <= N,
+ * holds X[i-1][j-1], X[i-1][j], X[i][j-1], X[i][j], pixels outside the grid being 0.
+ * Classes: every window is counted by its number n = 0 .. 4 of foreground pixels, the n = 2 windows apart as the two
+ * diagonal patterns (QD) and the four adjacent ones (Q2).
+ * Border count: the foreground pixels of row 0, plus row N-1, plus column 0, plus column N-1 (a corner pixel counts
+ * twice): the foreground pixel edges that lie on the box.
+ * Result: the seven int64 words Q0, Q1, Q2, QD, Q3, Q4, border at the indices below.  What follows from them is exact
+ * integer arithmetic and left to the caller (chsimpy_amd/morphology.py):
+ *   n_A = (Q1 + 2 Q2 + 2 QD + 3 Q3 + 4 Q4) / 4   foreground pixels; SA = n_A / N^2
+ *   perimeter = Q1 + Q2 + 2 QD + Q3               unit edges between foreground and background, the ring included
+ *   perimeter_inner = perimeter - border          4-adjacent unlike pixel pairs inside the grid
+ *   euler8 = (Q1 - Q3 - 2 QD) / 4                 8-connected foreground components minus 4-connected holes
+ *   euler4 = (Q1 - Q3 + 2 QD) / 4                 4-connected foreground components minus 8-connected holes
+ * Works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: one sweep that reads the
+ * field alone and writes buffers of its own, so the run does not notice it, and integer sums, so two looks return the
+ * same bits.  CHS_EINVAL for a null argument or a threshold that is not finite. */
+#define CHS_MORPH_WORDS 7
+#define CHS_MORPH_Q0 0
+#define CHS_MORPH_Q1 1
+#define CHS_MORPH_Q2 2
+#define CHS_MORPH_QD 3
+#define CHS_MORPH_Q3 4
+#define CHS_MORPH_Q4 5
+#define CHS_MORPH_BORDER 6
+int chs_morphology(chs_handle h, double threshold, int64_t out[CHS_MORPH_WORDS]);
+/* Device time (ms, HIP events) of the handle's last chs_morphology, both kernels.  CHS_ESTATE before the first look. */
+int chs_morphology_last_ms(chs_handle h, double* ms);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -318,6 +349,11 @@ int chs_batch_member_rows(chs_batch b, int32_t member, double* rows /*[n][9]*/, 
  * handle on the same field, and of the call with its own number.  The members' states, fields and records stay
  * untouched: their next call is bit for bit what it is without the look. */
 int chs_batch_structure_factor(chs_batch b, int32_t member, double* ssum /*[nbins] or [B][nbins]*/, int32_t nbins);
+/* chs_morphology of member `member` (threshold[1], out[CHS_MORPH_WORDS]), or of every member for member = -1
+ * (threshold[B], out[B][CHS_MORPH_WORDS]: one launch pair over all members, each with its own threshold).  Member by
+ * member the words are those of the member's single handle on the same field.  The members' states, fields and records
+ * stay untouched.  CHS_EINVAL for a member outside [-1, B). */
+int chs_batch_morphology(chs_batch b, int32_t member, const double* threshold, int64_t* out);
 
 #ifdef __cplusplus
 }
