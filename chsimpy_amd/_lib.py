@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libchs_hip.so')
 
-CHS_OK, CHS_EINVAL, CHS_EHIP, CHS_ENAN, CHS_ESTATE = 0, -1, -2, -3, -4
+CHS_OK, CHS_EINVAL, CHS_EHIP, CHS_ENAN, CHS_ESTATE, CHS_ECHECK = 0, -1, -2, -3, -4, -5
 CHS_F64, CHS_F32 = 0, 1
 CHS_ENGINE_AUTO, CHS_ENGINE_DIRECT, CHS_ENGINE_FAST, CHS_ENGINE_CHIRP = 0, 1, 2, 3
 CHS_CHIRP_AUTO_MIN_N = 129    # the smallest N that 'auto' gives to the chirp engine (include/chs_hip.h)
@@ -22,6 +22,9 @@ CHS_STEP_LAST_CALL = 4
 CHS_STEP_KEEP_T1 = 8
 CHS_NKERNELS = 8
 CHS_MORPH_WORDS = 7           # int64 words of chs_morphology: Q0, Q1, Q2, QD, Q3, Q4, border
+CHS_CC_WORDS = 7              # int64 words of chs_components: count, area, largest, sumsq, inner, spanning, largest_first
+CHS_CC_COLS = 6               # int32 columns of its table: first, area, imin, imax, jmin, jmax
+CHS_CC_BELOW, CHS_CC_ABOVE = 0, 1
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -39,6 +42,8 @@ SYMBOLS = (
     'chs_batch_step_n_queued', 'chs_batch_member_rows', 'chs_batch_engine',
     'chs_structure_factor_bins', 'chs_structure_factor', 'chs_structure_factor_last_ms', 'chs_batch_structure_factor',
     'chs_morphology', 'chs_morphology_last_ms', 'chs_batch_morphology',
+    'chs_components', 'chs_components_table', 'chs_components_labels', 'chs_components_last_ms', 'chs_components_tile',
+    'chs_batch_components', 'chs_batch_components_table', 'chs_batch_components_labels',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -162,6 +167,15 @@ def load():
     lib.chs_morphology.argtypes = [vp, C.c_double, i64p]
     lib.chs_morphology_last_ms.argtypes = [vp, dp]
     lib.chs_batch_morphology.argtypes = [vp, C.c_int32, dp, i64p]
+    i32p = C.POINTER(C.c_int32)
+    lib.chs_components.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, i64p]
+    lib.chs_components_table.argtypes = [vp, C.c_int64, i32p]
+    lib.chs_components_labels.argtypes = [vp, i32p]
+    lib.chs_components_last_ms.argtypes = [vp, dp]
+    lib.chs_components_tile.argtypes = [i32p, i32p]
+    lib.chs_batch_components.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, i64p]
+    lib.chs_batch_components_table.argtypes = [vp, C.c_int64, i32p]
+    lib.chs_batch_components_labels.argtypes = [vp, i32p]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -185,6 +199,25 @@ def _dptr(a):
 
 def _i64ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def components_tile():
+    """(rows, columns) of the tile a workgroup of chs_components labels in LDS (chs_components_tile)."""
+    r, c = C.c_int32(0), C.c_int32(0)
+    rc = load().chs_components_tile(C.byref(r), C.byref(c))
+    if rc != CHS_OK:
+        raise EngineError(f"chs_components_tile failed ({rc})")
+    return int(r.value), int(c.value)
+
+
+def __getattr__(name):
+    if name == 'CC_TILE':   # read from the library at the first use: importing the binding does not load it
+        return components_tile()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _as_f64(a, shape=None):
@@ -215,6 +248,7 @@ class Engine:
         self.lib = load()
         self.N = int(consts.N)
         self._h = C.c_void_p()
+        self._cc_count = 0
         lam = _as_f64(lam, (self.N,))
         rc = self.lib.chs_create(C.byref(consts), _dptr(lam), C.byref(self._h))
         self._check(rc, 'chs_create')
@@ -337,6 +371,37 @@ class Engine:
         self._check(self.lib.chs_morphology_last_ms(self._h, C.byref(ms)), 'chs_morphology_last_ms')
         return float(ms.value)
 
+    def components(self, threshold, connectivity=4, side=CHS_CC_BELOW):
+        """The seven int64 summary words of the connected components of the field the device holds (chs_components;
+        chsimpy_amd/components.py names them).  Table and labels of this look: `components_table`, `components_labels`."""
+        out = np.empty(CHS_CC_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_components(self._h, float(threshold), int(connectivity), int(side), _i64ptr(out)), 'chs_components')
+        self._cc_count = int(out[0])
+        return out
+
+    def components_table(self):
+        """int32 [count][6] of the last look: first, area, imin, imax, jmin, jmax."""
+        out = np.empty((self._cc_count, CHS_CC_COLS), dtype=np.int32)
+        self._check(self.lib.chs_components_table(self._h, self._cc_count, _i32ptr(out)), 'chs_components_table')
+        return out
+
+    def components_labels(self):
+        """int32 [N][N] of the last look: the component's number, -1 for background."""
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._check(self.lib.chs_components_labels(self._h, _i32ptr(out)), 'chs_components_labels')
+        return out
+
+    def components_look(self, threshold, connectivity, side, table=True, labels=False):
+        """One look with what belongs to it: (words, table or None, labels or None)."""
+        words = self.components(threshold, connectivity, side)
+        return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
+
+    def components_ms(self):
+        """Device time (ms) of the last `components`."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.chs_components_last_ms(self._h, C.byref(ms)), 'chs_components_last_ms')
+        return float(ms.value)
+
     @property
     def engine(self):
         return {CHS_ENGINE_DIRECT: 'direct', CHS_ENGINE_FAST: 'fast', CHS_ENGINE_CHIRP: 'chirp'}[self.lib.chs_engine(self._h)]
@@ -373,6 +438,7 @@ class Batch:
         self.B = len(consts_list)
         self.N = int(consts_list[0].N) if self.B else 0
         self._h = C.c_void_p()
+        self._cc_count = 0
         arr = (chs_consts * max(self.B, 1))(*consts_list)
         lam = _as_f64(lam, (self.N,))
         self._check(self.lib.chs_batch_create(arr, self.B, _dptr(lam), C.byref(self._h)), 'chs_batch_create')
@@ -469,6 +535,29 @@ class Batch:
         self._check(self.lib.chs_batch_morphology(self._h, -1 if member is None else int(member), _dptr(t), _i64ptr(out)),
                     'chs_batch_morphology')
         return out
+
+    def components(self, member, threshold, connectivity=4, side=CHS_CC_BELOW):
+        """`Engine.components` of one member (chs_batch_components): the batch has one set of buffers, so the table and
+        the labels are those of its last look."""
+        out = np.empty(CHS_CC_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_batch_components(self._h, int(member), float(threshold), int(connectivity), int(side),
+                                                  _i64ptr(out)), 'chs_batch_components')
+        self._cc_count = int(out[0])
+        return out
+
+    def components_table(self):
+        out = np.empty((self._cc_count, CHS_CC_COLS), dtype=np.int32)
+        self._check(self.lib.chs_batch_components_table(self._h, self._cc_count, _i32ptr(out)), 'chs_batch_components_table')
+        return out
+
+    def components_labels(self):
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._check(self.lib.chs_batch_components_labels(self._h, _i32ptr(out)), 'chs_batch_components_labels')
+        return out
+
+    def components_look(self, member, threshold, connectivity, side, table=True, labels=False):
+        words = self.components(member, threshold, connectivity, side)
+        return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
 
     def get_state(self, member):
         s = chs_state()

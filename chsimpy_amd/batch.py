@@ -124,6 +124,12 @@ class _Member:
     def morphology(self, threshold):
         return self._b.morphology(threshold, self._m)
 
+    def components(self, threshold, connectivity=4, side=0):
+        return self._b.components(self._m, threshold, connectivity, side)
+
+    def components_look(self, threshold, connectivity, side, table=True, labels=False):
+        return self._b.components_look(self._m, threshold, connectivity, side, table, labels)
+
     def close(self):
         pass  # (the batch owns the device state)
 
@@ -271,6 +277,24 @@ class BatchSolver:
             return morphology.Morphology(b.morphology(ts[member], member), s.params.N, ts[member], s.solution.delx)
         words = b.morphology(ts)
         return [morphology.Morphology(words[m], s.params.N, ts[m], s.solution.delx) for m, s in enumerate(self.solvers)]
+
+    def components(self, member=None, threshold=None, connectivity=4, side='below', table=True, labels=False):
+        """The members' connected components (`Solver.components`): a list of one `components.Components` per member,
+        looked at member by member on the batch's stream with the batch's one set of buffers, or the one of ``member``.
+        ``threshold``: one value for all, one per member, or None for every member's own ``params.threshold``.  The
+        members' runs do not notice the looks."""
+        self._get_batch()
+        if threshold is None:
+            ts = [None] * len(self.solvers)
+        elif np.ndim(threshold) == 0:
+            ts = [float(threshold)] * len(self.solvers)
+        else:
+            ts = [float(t) for t in threshold]
+            if len(ts) != len(self.solvers):
+                raise ValueError(f"{len(self.solvers)} thresholds are needed, got {len(ts)}")
+        if member is not None:
+            return self.solvers[member].components(ts[member], connectivity, side, table, labels)
+        return [s.components(t, connectivity, side, table, labels) for s, t in zip(self.solvers, ts)]
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

@@ -162,6 +162,7 @@ struct Batch {
   std::vector<std::vector<double>> qRows;  // the members' rows of the last queued call (chs_batch_member_rows)
   void* spec = nullptr;          // chs_batch_structure_factor of all members: its buffers (chs_spectrum.hip), at the first call
   void* morph = nullptr;         // chs_batch_morphology of all members: its buffers (chs_morphology.hip), at the first look
+  void* cc = nullptr;            // chs_batch_components: the batch's one set of buffers (chs_components.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -179,6 +180,7 @@ void batch_free(Batch* b) {
   }
   chs_spectrum_free(&b->spec);
   chs_morph_free(&b->morph);
+  chs_cc_free(&b->cc);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -797,4 +799,25 @@ extern "C" int chs_batch_morphology(chs_batch h, int32_t member, const double* t
   if (member < -1 || member >= b->B) return bad("chs_batch_morphology: no such member");
   if (member >= 0) return chs_morph_one(b->m[(size_t)member], threshold, out, "chs_batch_morphology");
   return chs_morph_all(b->m.data(), b->B, b->stream, &b->morph, threshold, out, "chs_batch_morphology");
+}
+
+// The components of one member: the single handle's look on the batch's stream, with the batch's one set of buffers.
+extern "C" int chs_batch_components(chs_batch h, int32_t member, double threshold, int32_t connectivity, int32_t side,
+                                    int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_components: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_components: no such member");
+  return chs_cc_look(b->m[(size_t)member], b->stream, &b->cc, threshold, connectivity, side, out, "chs_batch_components");
+}
+
+extern "C" int chs_batch_components_table(chs_batch h, int64_t rows, int32_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_components_table: null handle");
+  return chs_cc_table(b->cc, b->m[0]->hc.device, b->stream, rows, out, "chs_batch_components_table");
+}
+
+extern "C" int chs_batch_components_labels(chs_batch h, int32_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_components_labels: null handle");
+  return chs_cc_labels(b->cc, b->m[0]->hc.device, b->stream, out, "chs_batch_components_labels");
 }

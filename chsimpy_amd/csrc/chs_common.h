@@ -250,6 +250,7 @@ struct Engine {
   void* chirp = nullptr;       // chirp engine: its plan and tables (chs_chirp.hip)
   void* spec = nullptr;        // structure factor: partial bins, result, events (chs_spectrum.hip), at the first call
   void* morph = nullptr;       // morphology: tile partials, result, events (chs_morphology.hip), at the first look
+  void* cc = nullptr;          // connected components: labels, numbers, table, result, events (chs_components.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -408,3 +409,14 @@ int chs_morph_one(Engine* E, const double* threshold, int64_t* out, const char* 
 int chs_morph_all(Engine* const* m, int B, hipStream_t s, void** buf, const double* threshold, int64_t* out, const char* who);
 void chs_morph_free(void** buf);
 void chs_morph_forget(void* buf);   // the buffers stay, the time of the last look goes
+
+// ---- connected components (chs_components.hip) ---------------------------------
+// The components of E's field thresholded at `threshold` on stream `s` with the buffer set *buf
+// (the handle's own, or the batch's one set for whichever member it looks at), allocated here at the first look:
+// out[CHS_CC_WORDS].  Table and labels of the last look of a buffer set: chs_cc_table, chs_cc_labels.
+int chs_cc_look(Engine* E, hipStream_t s, void** buf, double threshold, int32_t connectivity, int32_t side, int64_t* out,
+                const char* who);
+int chs_cc_table(void* buf, int device, hipStream_t s, int64_t rows, int32_t* out, const char* who);
+int chs_cc_labels(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
+void chs_cc_free(void** buf);
+void chs_cc_forget(void* buf);   // the buffers stay, the last look goes

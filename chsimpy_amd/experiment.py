@@ -134,11 +134,25 @@ def _morphology_row(mo):
     return (mo.threshold, mo.n_A, mo.SA, mo.perimeter, mo.perimeter_inner, mo.euler8, mo.euler4)
 
 
+def _droplets_row(below, above):
+    """(threshold, connectivity, count, largest, spanning, mean_area below, the same four above) of a member's final
+    field: two chsimpy_amd.components.Components, one per side."""
+    return (below.threshold, below.connectivity, below.count, below.largest, below.spanning, below.mean_area,
+            above.count, above.largest, above.spanning, above.mean_area)
+
+
+def _droplets_of(solver, connectivity):
+    """The two summary-only looks behind a member's run."""
+    return _droplets_row(solver.components(connectivity=connectivity, side='below', table=False),
+                         solver.components(connectivity=connectivity, side='above', table=False))
+
+
 def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None,
-                       morphology=None):
+                       morphology=None, droplets=None, droplets_connectivity=4):
     """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains`` (a dict): the
     member's domain size, measured on the device behind its run, goes to ``domains[run_id]``; ``morphology`` (a dict):
-    likewise the morphology of its final field at ``params.threshold``."""
+    likewise the morphology of its final field at ``params.threshold``; ``droplets`` (a dict): likewise its connected
+    components on both sides of that threshold (summary-only looks, ``droplets_connectivity`` 4 or 8)."""
     from .simulator import Simulator
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
@@ -148,6 +162,8 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
             domains[run_id] = _domain_row(simulator.solver.structure_factor())
         if morphology is not None:
             morphology[run_id] = _morphology_row(simulator.solver.morphology())
+        if droplets is not None:
+            droplets[run_id] = _droplets_of(simulator.solver, droplets_connectivity)
         simulator.export()
         rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
@@ -157,11 +173,12 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
 
 
 def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None,
-                  morphology=None):
+                  morphology=None, droplets=None, droplets_connectivity=4):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
     members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``,
-    ``morphology``: as in run_experiment_gpu, each from one device pass over the group."""
+    ``morphology``: as in run_experiment_gpu, each from one device pass over the group; ``droplets``: as there, member by
+    member on the batch's stream."""
     from .batch import BatchSolver
     from .simulator import Simulator
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
@@ -175,6 +192,9 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
         if morphology is not None:
             for i, mo in zip(run_ids, bs.morphology()):
                 morphology[i] = _morphology_row(mo)
+        if droplets is not None:
+            for i, s in zip(run_ids, bs.solvers):
+                droplets[i] = _droplets_of(s, droplets_connectivity)
         recs = []
         for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
             # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
@@ -251,6 +271,40 @@ def gather_morphology(local, nr_items, rank, world, dist=None, device='cpu'):
     return sorted((int(r[0]),) + r[1:] for r in got)
 
 
+DROPLETS_COLS = ('id', 'threshold', 'connectivity', 'count_below', 'largest_below', 'spanning_below', 'mean_area_below',
+                 'count_above', 'largest_above', 'spanning_above', 'mean_area_above')
+
+
+def gather_droplets(local, nr_items, rank, world, dist=None, device='cpu'):
+    """The members' DROPLETS_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the ten values
+    behind the id.  One all_gather of a float64 block per rank, as gather_morphology (the counts are integers below
+    2^53: exact in float64)."""
+    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
+    if world == 1 or dist is None:
+        return rows
+    import torch
+    per = (nr_items + world - 1) // world
+    buf = torch.full((per, len(DROPLETS_COLS)), float('nan'), dtype=torch.float64, device=device)
+    for k, row in enumerate(rows):
+        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
+    out = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(out, buf)
+    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
+    return sorted((int(r[0]),) + r[1:] for r in got)
+
+
+def write_droplets(file_id, rows):
+    """``<file_id>-droplets.csv``: DROPLETS_COLS per member (--droplets), the counts as integers, the floats written so
+    that they read back exactly."""
+    name = f"{file_id}-droplets.csv"
+    with open(name, 'w') as f:
+        f.write(','.join(DROPLETS_COLS) + "\n")
+        for i, t, conn, cb, lb, sb, mb, ca, la, sa, ma in rows:
+            f.write(f"{int(i)},{float(t)!r},{int(conn)},{int(cb)},{int(lb)},{int(sb)},{float(mb)!r},"
+                    f"{int(ca)},{int(la)},{int(sa)},{float(ma)!r}\n")
+    return name
+
+
 def write_morphology(file_id, rows):
     """``<file_id>-morphology.csv``: MORPHOLOGY_COLS per member (--morphology), the counts as integers, the two floats
     written so that they read back exactly."""
@@ -297,7 +351,8 @@ def write_results(file_id, records):
 
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
-                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None, morphology=None):
+                 concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None, morphology=None,
+                 droplets=None, droplets_connectivity=4):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -323,11 +378,17 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
 
     ``morphology`` (a dict, with the default run functions): likewise the morphology of every member's final field at
     its ``params.threshold`` -- area, interface length, Euler numbers (chsimpy_amd/morphology.py) -- in
-    ``morphology[run_id]`` (gather_morphology)."""
+    ``morphology[run_id]`` (gather_morphology).
+
+    ``droplets`` (a dict, with the default run functions): likewise the connected components of every member's final
+    field on both sides of its ``params.threshold`` -- count, largest, spanning, mean area (chsimpy_amd/components.py),
+    at ``droplets_connectivity`` -- in ``droplets[run_id]`` (gather_droplets)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     dom = {} if domains is None else {'domains': domains}   # (the run functions are called as ever without it)
     if morphology is not None:
         dom['morphology'] = morphology
+    if droplets is not None:
+        dom['droplets'], dom['droplets_connectivity'] = droplets, int(droplets_connectivity)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
             return run_experiment_gpu(run_id, p, rv, al, U_init, **dom)
@@ -422,6 +483,10 @@ def main(argv=None):
     ap.add_argument('--morphology', action='store_true', help='measure the morphology of every member\'s final field on the '
                     'device behind its run (bit-quad counts of the field below the threshold): <id>-morphology.csv with id, '
                     'threshold, n_A, SA, perimeter, perimeter_inner, euler8, euler4')
+    ap.add_argument('--droplets', action='store_true', help='label the connected components of every member\'s final field on '
+                    'the device behind its run, on both sides of the threshold: <id>-droplets.csv with id, threshold, '
+                    'connectivity, and count, largest, spanning, mean_area below and above')
+    ap.add_argument('--droplets-connectivity', type=int, choices=(4, 8), default=4, help='the connectivity of --droplets')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
     ap.add_argument('--backend', default=os.environ.get('CHS_DIST_BACKEND', 'nccl'),
@@ -474,11 +539,13 @@ def main(argv=None):
                        + (["dry_run, True"] if a.dry_run else []))
     domains = {} if a.domain_size else None
     morph = {} if a.morphology else None
+    drops = {} if a.droplets else None
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
                            batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
                            queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains,
-                           **({} if morph is None else {'morphology': morph}))
+                           **({} if morph is None else {'morphology': morph}),
+                           **({} if drops is None else {'droplets': drops, 'droplets_connectivity': a.droplets_connectivity}))
     if domains is not None:
         if a.dry_run:   # (members without device work: a function of the run id, as their records are)
             nr = make_rand_values(ep)[2]
@@ -490,6 +557,12 @@ def main(argv=None):
             morph = {i: (float(p.threshold), p.N * p.N - i, (p.N * p.N - i) / (p.N * p.N), 4 * p.N + 4 * i, 4 * i, 1 - i, 1 - i)
                      for i in my_run_ids(nr, rank, world)}
         morphology_rows = gather_morphology(morph, nr, rank, world, dist, device)
+    if drops is not None:
+        nr = make_rand_values(ep)[2]
+        if a.dry_run:   # (made up from the run id, as above: i + 1 droplets of 3 pixels in a spanning matrix with i holes)
+            drops = {i: (float(p.threshold), a.droplets_connectivity, i + 1, 3, 0, 3.0, 1, p.N * p.N - 3 * (i + 1), 1,
+                         float(p.N * p.N - 3 * (i + 1))) for i in my_run_ids(nr, rank, world)}
+        droplets_rows = gather_droplets(drops, nr, rank, world, dist, device)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)
@@ -501,6 +574,8 @@ def main(argv=None):
             print(f"  {write_domains(p.file_id, domain_rows)}")
         if morph is not None:
             print(f"  {write_morphology(p.file_id, morphology_rows)}")
+        if drops is not None:
+            print(f"  {write_droplets(p.file_id, droplets_rows)}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

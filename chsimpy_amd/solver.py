@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, morphology, mport, spectrum
+from . import _lib, components, morphology, mport, spectrum
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -174,6 +174,20 @@ class Solver:
         eng = self._get_engine()
         self._push_edited_U()
         return morphology.Morphology(eng.morphology(t), self.params.N, t, self.solution.delx)
+
+    def components(self, threshold=None, connectivity=4, side='below', table=True, labels=False):
+        """The connected components of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): droplet count, sizes, bounding boxes, spanning -- a self-contained
+        `components.Components` from one look on the device between two calls, which the run does not notice.
+        ``side='below'`` is the foreground of `morphology`, ``'above'`` its complement; ``connectivity`` 4 or 8; the
+        table (one row per component) and the label image are fetched in this call when asked for.  A field the host
+        edited is pushed first, as solve_or_resume does.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        conn, code = components.check_connectivity(connectivity), components.side_code(side)
+        eng = self._get_engine()
+        self._push_edited_U()
+        words, tab, lab = eng.components_look(t, conn, code, table, labels)
+        return components.Components(words, self.params.N, t, conn, code, table=tab, labels=lab, delx=self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

@@ -36,6 +36,7 @@ extern "C" {
 #define CHS_ENAN (-3)     /* a recorded scalar became NaN (chsimpy/timedata.py:10) */
 #define CHS_ESTATE (-4)   /* call order violated (e.g. step before prepare:
                              the assert at chsimpy/solver.py:139)                */
+#define CHS_ECHECK (-5)   /* a self-check of a device result failed (chs_components) */
 
 /* arithmetic type of the device path */
 #define CHS_F64 0
@@ -283,6 +284,56 @@ int chs_morphology(chs_handle h, double threshold, int64_t out[CHS_MORPH_WORDS])
 /* Device time (ms, HIP events) of the handle's last chs_morphology, both kernels.  CHS_ESTATE before the first look. */
 int chs_morphology_last_ms(chs_handle h, double* ms);
 
+/* ---- Connected components of the thresholded field: droplet count, sizes, spanning ---------
+ * Foreground, for the N x N field U and a finite threshold t:
+ *   side = CHS_CC_BELOW: X[i][j] = ((double)U[i][j] < t), exactly the foreground of chs_morphology: a NaN pixel and a
+ *     pixel equal to t are background;
+ *   side = CHS_CC_ABOVE: the complement inside the grid, !((double)U[i][j] < t): a NaN pixel and a pixel equal to t
+ *     are foreground.
+ * Connectivity: 4 joins edge neighbours, 8 joins edge and corner neighbours.  No wrap-around; nothing outside the grid
+ * is foreground.
+ * Components: a component is a maximal connected set of foreground pixels; its `first` is the smallest linear index
+ * i*N + j of its pixels; the components are numbered 0 .. C-1 by ascending `first`.  That numbering is unique, so a
+ * look returns the same bits at every call, whatever order the device worked in.
+ * Table: one row of CHS_CC_COLS int32 per component: first, area, imin, imax, jmin, jmax (the bounding box, inclusive).
+ * Summary: CHS_CC_WORDS int64 words at the indices below:
+ *   COUNT          C
+ *   AREA           foreground pixels = the sum of the areas
+ *   LARGEST        the largest area, 0 if there is no component
+ *   SUMSQ          the sum of area^2 (at most N^4: fits up to N = 8192)
+ *   INNER          components whose bounding box touches none of rows 0 and N-1 and columns 0 and N-1
+ *   SPANNING       components with imin == 0 && imax == N-1, or jmin == 0 && jmax == N-1
+ *   LARGEST_FIRST  the `first` of the largest component, the smallest `first` on a tie, -1 if there is none
+ * Labels: int32 [N][N], the component number of the pixel, -1 for background.
+ * With the words of chs_morphology at the same t: euler8 = COUNT(below, 8) - INNER(above, 4) and
+ * euler4 = COUNT(below, 4) - INNER(above, 8).
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone and writes buffers of its own (allocated at the first look, freed with the handle), so the run does not notice
+ * it; everything is integer, so two looks return the same bits.  Table and labels of the last look stay available as a
+ * snapshot until the next look.  Every look checks its own labelling in the sweep that gathers the table (equal labels
+ * across every joined pixel pair, every label a root no larger than its pixel) and the caps of its loops: a failed
+ * check returns CHS_ECHECK and chs_last_error says which.  CHS_EINVAL for a null argument, a threshold that is not
+ * finite, a connectivity other than 4 or 8, a side other than 0 or 1, N above 16384, or `rows` not the COUNT of the
+ * last look; CHS_ESTATE for _table / _labels / _last_ms without a look. */
+#define CHS_CC_WORDS 7
+#define CHS_CC_COUNT 0
+#define CHS_CC_AREA 1
+#define CHS_CC_LARGEST 2
+#define CHS_CC_SUMSQ 3
+#define CHS_CC_INNER 4
+#define CHS_CC_SPANNING 5
+#define CHS_CC_LARGEST_FIRST 6
+#define CHS_CC_COLS 6
+#define CHS_CC_BELOW 0
+#define CHS_CC_ABOVE 1
+int chs_components(chs_handle h, double threshold, int32_t connectivity, int32_t side, int64_t out[CHS_CC_WORDS]);
+int chs_components_table(chs_handle h, int64_t rows, int32_t* out);   /* [rows][CHS_CC_COLS]; rows == COUNT of the last look */
+int chs_components_labels(chs_handle h, int32_t* out);                /* [N][N] of the last look */
+/* Device time (ms, HIP events) of the handle's last look, first launch to last (the host's wait for the count in it). */
+int chs_components_last_ms(chs_handle h, double* ms);
+/* The extents of the tile a workgroup labels in LDS (what the tests size their fields by). */
+int chs_components_tile(int32_t* rows, int32_t* cols);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -354,6 +405,12 @@ int chs_batch_structure_factor(chs_batch b, int32_t member, double* ssum /*[nbin
  * member the words are those of the member's single handle on the same field.  The members' states, fields and records
  * stay untouched.  CHS_EINVAL for a member outside [-1, B). */
 int chs_batch_morphology(chs_batch b, int32_t member, const double* threshold, int64_t* out);
+/* chs_components of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of buffers for the batch,
+ * so table and labels are those of the batch's last look, whichever member it was.  The words, the table and the labels
+ * are those of the member's single handle on the same field.  The members' states, fields and records stay untouched. */
+int chs_batch_components(chs_batch b, int32_t member, double threshold, int32_t connectivity, int32_t side, int64_t out[CHS_CC_WORDS]);
+int chs_batch_components_table(chs_batch b, int64_t rows, int32_t* out);
+int chs_batch_components_labels(chs_batch b, int32_t* out);
 
 #ifdef __cplusplus
 }
