@@ -25,6 +25,8 @@ CHS_MORPH_WORDS = 7           # int64 words of chs_morphology: Q0, Q1, Q2, QD, Q
 CHS_CC_WORDS = 7              # int64 words of chs_components: count, area, largest, sumsq, inner, spanning, largest_first
 CHS_CC_COLS = 6               # int32 columns of its table: first, area, imin, imax, jmin, jmax
 CHS_CC_BELOW, CHS_CC_ABOVE = 0, 1
+CHS_DT_WORDS = 5              # int64 words of chs_distance: fg, d2max, d2max_first, sumd2, ninf
+CHS_DT_INF = 1 << 30          # D2 of every pixel of a grid without background
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -44,6 +46,8 @@ SYMBOLS = (
     'chs_morphology', 'chs_morphology_last_ms', 'chs_batch_morphology',
     'chs_components', 'chs_components_table', 'chs_components_labels', 'chs_components_last_ms', 'chs_components_tile',
     'chs_batch_components', 'chs_batch_components_table', 'chs_batch_components_labels',
+    'chs_distance_bins', 'chs_distance', 'chs_distance_hist', 'chs_distance_map', 'chs_distance_last_ms', 'chs_distance_tile',
+    'chs_batch_distance', 'chs_batch_distance_hist', 'chs_batch_distance_map',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -176,6 +180,16 @@ def load():
     lib.chs_batch_components.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, i64p]
     lib.chs_batch_components_table.argtypes = [vp, C.c_int64, i32p]
     lib.chs_batch_components_labels.argtypes = [vp, i32p]
+    lib.chs_distance_bins.argtypes = [C.c_int32]
+    lib.chs_distance_bins.restype = C.c_int32
+    lib.chs_distance.argtypes = [vp, C.c_double, C.c_int32, i64p]
+    lib.chs_distance_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_distance_map.argtypes = [vp, i32p]
+    lib.chs_distance_last_ms.argtypes = [vp, dp]
+    lib.chs_distance_tile.argtypes = [i32p, i32p]
+    lib.chs_batch_distance.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, i64p]
+    lib.chs_batch_distance_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_batch_distance_map.argtypes = [vp, i32p]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -212,6 +226,21 @@ def components_tile():
     if rc != CHS_OK:
         raise EngineError(f"chs_components_tile failed ({rc})")
     return int(r.value), int(c.value)
+
+
+def distance_tile():
+    """(band_rows, row_chunk) of the kernels of chs_distance (chs_distance_tile): the rows of a band of the vertical pass
+    and the consecutive pixels one wavefront pass of the horizontal pass covers."""
+    b, c = C.c_int32(0), C.c_int32(0)
+    rc = load().chs_distance_tile(C.byref(b), C.byref(c))
+    if rc != CHS_OK:
+        raise EngineError(f"chs_distance_tile failed ({rc})")
+    return int(b.value), int(c.value)
+
+
+def distance_bins(N):
+    """The length of the histogram of chs_distance at grid size N (chs_distance_bins)."""
+    return int(load().chs_distance_bins(int(N)))
 
 
 def __getattr__(name):
@@ -396,6 +425,36 @@ class Engine:
         words = self.components(threshold, connectivity, side)
         return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
 
+    def distance(self, threshold, side=CHS_CC_BELOW):
+        """The five int64 summary words of the distance transform of the field the device holds (chs_distance;
+        chsimpy_amd/distance.py names them).  Histogram and map of this look: `distance_hist`, `distance_map`."""
+        out = np.empty(CHS_DT_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_distance(self._h, float(threshold), int(side), _i64ptr(out)), 'chs_distance')
+        return out
+
+    def distance_hist(self):
+        """int64 [chs_distance_bins(N)] of the last look: the foreground pixels by radius bin."""
+        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
+        self._check(self.lib.chs_distance_hist(self._h, len(out), _i64ptr(out)), 'chs_distance_hist')
+        return out
+
+    def distance_map(self):
+        """int32 [N][N] of the last look: the squared distances."""
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._check(self.lib.chs_distance_map(self._h, _i32ptr(out)), 'chs_distance_map')
+        return out
+
+    def distance_look(self, threshold, side, hist=True, map=False):
+        """One look with what belongs to it: (words, histogram or None, map or None)."""
+        words = self.distance(threshold, side)
+        return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
+
+    def distance_ms(self):
+        """Device time (ms) of the last `distance`."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.chs_distance_last_ms(self._h, C.byref(ms)), 'chs_distance_last_ms')
+        return float(ms.value)
+
     def components_ms(self):
         """Device time (ms) of the last `components`."""
         ms = C.c_double(0.0)
@@ -558,6 +617,28 @@ class Batch:
     def components_look(self, member, threshold, connectivity, side, table=True, labels=False):
         words = self.components(member, threshold, connectivity, side)
         return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
+
+    def distance(self, member, threshold, side=CHS_CC_BELOW):
+        """`Engine.distance` of one member (chs_batch_distance): the batch has one set of buffers, so the histogram and
+        the map are those of its last look."""
+        out = np.empty(CHS_DT_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_batch_distance(self._h, int(member), float(threshold), int(side), _i64ptr(out)),
+                    'chs_batch_distance')
+        return out
+
+    def distance_hist(self):
+        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
+        self._check(self.lib.chs_batch_distance_hist(self._h, len(out), _i64ptr(out)), 'chs_batch_distance_hist')
+        return out
+
+    def distance_map(self):
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._check(self.lib.chs_batch_distance_map(self._h, _i32ptr(out)), 'chs_batch_distance_map')
+        return out
+
+    def distance_look(self, member, threshold, side, hist=True, map=False):
+        words = self.distance(member, threshold, side)
+        return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
 
     def get_state(self, member):
         s = chs_state()

@@ -130,6 +130,12 @@ class _Member:
     def components_look(self, threshold, connectivity, side, table=True, labels=False):
         return self._b.components_look(self._m, threshold, connectivity, side, table, labels)
 
+    def distance(self, threshold, side=0):
+        return self._b.distance(self._m, threshold, side)
+
+    def distance_look(self, threshold, side, hist=True, map=False):
+        return self._b.distance_look(self._m, threshold, side, hist, map)
+
     def close(self):
         pass  # (the batch owns the device state)
 
@@ -278,23 +284,39 @@ class BatchSolver:
         words = b.morphology(ts)
         return [morphology.Morphology(words[m], s.params.N, ts[m], s.solution.delx) for m, s in enumerate(self.solvers)]
 
+    def _member_thresholds(self, threshold):
+        """One threshold per member of a look that goes member by member: None (the member's own ``params.threshold``)
+        for None, the one value for all, or the given list."""
+        if threshold is None:
+            return [None] * len(self.solvers)
+        if np.ndim(threshold) == 0:
+            return [float(threshold)] * len(self.solvers)
+        ts = [float(t) for t in threshold]
+        if len(ts) != len(self.solvers):
+            raise ValueError(f"{len(self.solvers)} thresholds are needed, got {len(ts)}")
+        return ts
+
     def components(self, member=None, threshold=None, connectivity=4, side='below', table=True, labels=False):
         """The members' connected components (`Solver.components`): a list of one `components.Components` per member,
         looked at member by member on the batch's stream with the batch's one set of buffers, or the one of ``member``.
         ``threshold``: one value for all, one per member, or None for every member's own ``params.threshold``.  The
         members' runs do not notice the looks."""
         self._get_batch()
-        if threshold is None:
-            ts = [None] * len(self.solvers)
-        elif np.ndim(threshold) == 0:
-            ts = [float(threshold)] * len(self.solvers)
-        else:
-            ts = [float(t) for t in threshold]
-            if len(ts) != len(self.solvers):
-                raise ValueError(f"{len(self.solvers)} thresholds are needed, got {len(ts)}")
+        ts = self._member_thresholds(threshold)
         if member is not None:
             return self.solvers[member].components(ts[member], connectivity, side, table, labels)
         return [s.components(t, connectivity, side, table, labels) for s, t in zip(self.solvers, ts)]
+
+    def distance(self, member=None, threshold=None, side='below', hist=True, map=False):
+        """The members' distance transforms (`Solver.distance`): a list of one `distance.Distance` per member, looked at
+        member by member on the batch's stream with the batch's one set of buffers, or the one of ``member``.
+        ``threshold``: one value for all, one per member, or None for every member's own ``params.threshold``.  The
+        members' runs do not notice the looks."""
+        self._get_batch()
+        ts = self._member_thresholds(threshold)
+        if member is not None:
+            return self.solvers[member].distance(ts[member], side, hist, map)
+        return [s.distance(t, side, hist, map) for s, t in zip(self.solvers, ts)]
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

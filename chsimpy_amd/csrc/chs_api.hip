@@ -88,6 +88,7 @@ static void free_engine(Engine* E) {
   chs_spectrum_free(&E->spec);
   chs_morph_free(&E->morph);
   chs_cc_free(&E->cc);
+  chs_dt_free(&E->dt);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
   hipFree(E->dT1); hipFree(E->dHat);
   if (E->dHat2) hipFree(E->dHat2);
@@ -189,6 +190,7 @@ static int rearm(Engine* E, const chs_consts* c) {
   E->nColMinCur = 0; E->lastStepMs = 0.0; E->timer.on = false;
   chs_morph_forget(E->morph);   // (a handle from the pool has had no look: chs_morphology_last_ms)
   chs_cc_forget(E->cc);
+  chs_dt_forget(E->dt);
   read_env_hooks(E);
   if (E->engine == CHS_ENGINE_FAST) return chs_fast_rearm(E);
   return CHS_OK;

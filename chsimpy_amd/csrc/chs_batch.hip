@@ -163,6 +163,7 @@ struct Batch {
   void* spec = nullptr;          // chs_batch_structure_factor of all members: its buffers (chs_spectrum.hip), at the first call
   void* morph = nullptr;         // chs_batch_morphology of all members: its buffers (chs_morphology.hip), at the first look
   void* cc = nullptr;            // chs_batch_components: the batch's one set of buffers (chs_components.hip), at the first look
+  void* dt = nullptr;            // chs_batch_distance: the batch's one set of buffers (chs_distance.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -181,6 +182,7 @@ void batch_free(Batch* b) {
   chs_spectrum_free(&b->spec);
   chs_morph_free(&b->morph);
   chs_cc_free(&b->cc);
+  chs_dt_free(&b->dt);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -820,4 +822,24 @@ extern "C" int chs_batch_components_labels(chs_batch h, int32_t* out) {
   Batch* b = as_batch(h);
   if (!b) return bad("chs_batch_components_labels: null handle");
   return chs_cc_labels(b->cc, b->m[0]->hc.device, b->stream, out, "chs_batch_components_labels");
+}
+
+// The distance transform of one member: the single handle's look on the batch's stream, with the batch's one set of buffers.
+extern "C" int chs_batch_distance(chs_batch h, int32_t member, double threshold, int32_t side, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_distance: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_distance: no such member");
+  return chs_dt_look(b->m[(size_t)member], b->stream, &b->dt, threshold, side, out, "chs_batch_distance");
+}
+
+extern "C" int chs_batch_distance_hist(chs_batch h, int32_t nbins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_distance_hist: null handle");
+  return chs_dt_hist(b->dt, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_distance_hist");
+}
+
+extern "C" int chs_batch_distance_map(chs_batch h, int32_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_distance_map: null handle");
+  return chs_dt_map(b->dt, b->m[0]->hc.device, b->stream, out, "chs_batch_distance_map");
 }

@@ -251,6 +251,7 @@ struct Engine {
   void* spec = nullptr;        // structure factor: partial bins, result, events (chs_spectrum.hip), at the first call
   void* morph = nullptr;       // morphology: tile partials, result, events (chs_morphology.hip), at the first look
   void* cc = nullptr;          // connected components: labels, numbers, table, result, events (chs_components.hip), at the first look
+  void* dt = nullptr;          // distance transform: band masks, carries, D2, histogram, result, events (chs_distance.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -420,3 +421,13 @@ int chs_cc_table(void* buf, int device, hipStream_t s, int64_t rows, int32_t* ou
 int chs_cc_labels(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
 void chs_cc_free(void** buf);
 void chs_cc_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- distance transform (chs_distance.hip) -----------------------------------
+// The squared distances of E's field thresholded at `threshold` on stream `s` with the buffer set
+// *buf (the handle's own, or the batch's one set), allocated here at the first look: out[CHS_DT_WORDS].  Histogram and
+// map of the last look of a buffer set: chs_dt_hist, chs_dt_map.
+int chs_dt_look(Engine* E, hipStream_t s, void** buf, double threshold, int32_t side, int64_t* out, const char* who);
+int chs_dt_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
+int chs_dt_map(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
+void chs_dt_free(void** buf);
+void chs_dt_forget(void* buf);   // the buffers stay, the last look goes

@@ -147,12 +147,29 @@ def _droplets_of(solver, connectivity):
                          solver.components(connectivity=connectivity, side='above', table=False))
 
 
+def _widths_side(di):
+    """(fg, r_max, r2_mean, r_floor_mean, q50, q90) of one chsimpy_amd.distance.Distance with its histogram; NaN and -1
+    where the side has no pixel with a finite distance."""
+    if not di.finite:
+        return (di.fg, float('nan'), float('nan'), float('nan'), -1, -1)
+    return (di.fg, di.r_max, di.r2_mean, di.r_floor_mean, di.quantile(0.5), di.quantile(0.9))
+
+
+def _widths_of(solver):
+    """(threshold, the six values below, the six above) of a member's final field: two looks behind its run, summary and
+    histogram alone."""
+    below, above = solver.distance(side='below'), solver.distance(side='above')
+    return (below.threshold,) + _widths_side(below) + _widths_side(above)
+
+
 def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None,
-                       morphology=None, droplets=None, droplets_connectivity=4):
+                       morphology=None, droplets=None, droplets_connectivity=4, widths=None):
     """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains`` (a dict): the
     member's domain size, measured on the device behind its run, goes to ``domains[run_id]``; ``morphology`` (a dict):
     likewise the morphology of its final field at ``params.threshold``; ``droplets`` (a dict): likewise its connected
-    components on both sides of that threshold (summary-only looks, ``droplets_connectivity`` 4 or 8)."""
+    components on both sides of that threshold (summary-only looks, ``droplets_connectivity`` 4 or 8); ``widths`` (a
+    dict): likewise the distance transform on both sides of it (widest point, mean squared radius, radius-bin mean and
+    quantiles)."""
     from .simulator import Simulator
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
@@ -164,6 +181,8 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
             morphology[run_id] = _morphology_row(simulator.solver.morphology())
         if droplets is not None:
             droplets[run_id] = _droplets_of(simulator.solver, droplets_connectivity)
+        if widths is not None:
+            widths[run_id] = _widths_of(simulator.solver)
         simulator.export()
         rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
@@ -173,12 +192,12 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
 
 
 def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None,
-                  morphology=None, droplets=None, droplets_connectivity=4):
+                  morphology=None, droplets=None, droplets_connectivity=4, widths=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
     members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``,
-    ``morphology``: as in run_experiment_gpu, each from one device pass over the group; ``droplets``: as there, member by
-    member on the batch's stream."""
+    ``morphology``: as in run_experiment_gpu, each from one device pass over the group; ``droplets``, ``widths``: as
+    there, member by member on the batch's stream."""
     from .batch import BatchSolver
     from .simulator import Simulator
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
@@ -195,6 +214,9 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
         if droplets is not None:
             for i, s in zip(run_ids, bs.solvers):
                 droplets[i] = _droplets_of(s, droplets_connectivity)
+        if widths is not None:
+            for i, s in zip(run_ids, bs.solvers):
+                widths[i] = _widths_of(s)
         recs = []
         for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
             # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
@@ -305,6 +327,42 @@ def write_droplets(file_id, rows):
     return name
 
 
+WIDTHS_COLS = ('id', 'threshold') + tuple(f"{k}_{side}" for side in ('below', 'above')
+                                          for k in ('fg', 'r_max', 'r2_mean', 'r_floor_mean', 'q50', 'q90'))
+
+
+def gather_widths(local, nr_items, rank, world, dist=None, device='cpu'):
+    """The members' WIDTHS_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the thirteen
+    values behind the id.  One all_gather of a float64 block per rank, as gather_droplets (the counts are integers below
+    2^53: exact in float64; a side without a finite distance has NaN there, which only the id column is tested for)."""
+    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
+    if world == 1 or dist is None:
+        return rows
+    import torch
+    per = (nr_items + world - 1) // world
+    buf = torch.full((per, len(WIDTHS_COLS)), float('nan'), dtype=torch.float64, device=device)
+    for k, row in enumerate(rows):
+        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
+    out = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(out, buf)
+    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
+    return sorted((int(r[0]),) + r[1:] for r in got)
+
+
+def write_widths(file_id, rows):
+    """``<file_id>-widths.csv``: WIDTHS_COLS per member (--widths), the counts and quantiles as integers, the floats
+    written so that they read back exactly."""
+    name = f"{file_id}-widths.csv"
+    with open(name, 'w') as f:
+        f.write(','.join(WIDTHS_COLS) + "\n")
+        for row in rows:
+            i, t, sides = row[0], row[1], (row[2:8], row[8:14])
+            f.write(f"{int(i)},{float(t)!r}" + ''.join(
+                f",{int(fg)},{float(rm)!r},{float(r2)!r},{float(rf)!r},{int(q50)},{int(q90)}"
+                for fg, rm, r2, rf, q50, q90 in sides) + "\n")
+    return name
+
+
 def write_morphology(file_id, rows):
     """``<file_id>-morphology.csv``: MORPHOLOGY_COLS per member (--morphology), the counts as integers, the two floats
     written so that they read back exactly."""
@@ -352,7 +410,7 @@ def write_results(file_id, records):
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
                  concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None, morphology=None,
-                 droplets=None, droplets_connectivity=4):
+                 droplets=None, droplets_connectivity=4, widths=None):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -382,13 +440,19 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
 
     ``droplets`` (a dict, with the default run functions): likewise the connected components of every member's final
     field on both sides of its ``params.threshold`` -- count, largest, spanning, mean area (chsimpy_amd/components.py),
-    at ``droplets_connectivity`` -- in ``droplets[run_id]`` (gather_droplets)."""
+    at ``droplets_connectivity`` -- in ``droplets[run_id]`` (gather_droplets).
+
+    ``widths`` (a dict, with the default run functions): likewise the distance transform of every member's final field
+    on both sides of its ``params.threshold`` -- foreground, widest point, mean squared radius, radius-bin mean and
+    quantiles (chsimpy_amd/distance.py) -- in ``widths[run_id]`` (gather_widths)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     dom = {} if domains is None else {'domains': domains}   # (the run functions are called as ever without it)
     if morphology is not None:
         dom['morphology'] = morphology
     if droplets is not None:
         dom['droplets'], dom['droplets_connectivity'] = droplets, int(droplets_connectivity)
+    if widths is not None:
+        dom['widths'] = widths
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
             return run_experiment_gpu(run_id, p, rv, al, U_init, **dom)
@@ -486,6 +550,9 @@ def main(argv=None):
     ap.add_argument('--droplets', action='store_true', help='label the connected components of every member\'s final field on '
                     'the device behind its run, on both sides of the threshold: <id>-droplets.csv with id, threshold, '
                     'connectivity, and count, largest, spanning, mean_area below and above')
+    ap.add_argument('--widths', action='store_true', help='measure the exact Euclidean distance transform of every member\'s '
+                    'final field on the device behind its run, on both sides of the threshold: <id>-widths.csv with id, '
+                    'threshold, and fg, r_max, r2_mean, r_floor_mean, q50, q90 (radius-bin quantiles) below and above')
     ap.add_argument('--droplets-connectivity', type=int, choices=(4, 8), default=4, help='the connectivity of --droplets')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
@@ -540,12 +607,14 @@ def main(argv=None):
     domains = {} if a.domain_size else None
     morph = {} if a.morphology else None
     drops = {} if a.droplets else None
+    wid = {} if a.widths else None
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
                            batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
                            queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains,
                            **({} if morph is None else {'morphology': morph}),
-                           **({} if drops is None else {'droplets': drops, 'droplets_connectivity': a.droplets_connectivity}))
+                           **({} if drops is None else {'droplets': drops, 'droplets_connectivity': a.droplets_connectivity}),
+                           **({} if wid is None else {'widths': wid}))
     if domains is not None:
         if a.dry_run:   # (members without device work: a function of the run id, as their records are)
             nr = make_rand_values(ep)[2]
@@ -563,6 +632,13 @@ def main(argv=None):
             drops = {i: (float(p.threshold), a.droplets_connectivity, i + 1, 3, 0, 3.0, 1, p.N * p.N - 3 * (i + 1), 1,
                          float(p.N * p.N - 3 * (i + 1))) for i in my_run_ids(nr, rank, world)}
         droplets_rows = gather_droplets(drops, nr, rank, world, dist, device)
+    if wid is not None:
+        nr = make_rand_values(ep)[2]
+        if a.dry_run:   # (made up from the run id, as above: i + 1 pixels below, each its own distance 1; a matrix i + 2 wide)
+            wid = {i: (float(p.threshold), i + 1, 1.0, 1.0, 1.0, 1, 1,
+                       p.N * p.N - (i + 1), float(i + 2), 0.5 * (i + 2) ** 2, 0.5 * (i + 2), (i + 2) // 2, i + 2)
+                   for i in my_run_ids(nr, rank, world)}
+        widths_rows = gather_widths(wid, nr, rank, world, dist, device)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)
@@ -576,6 +652,8 @@ def main(argv=None):
             print(f"  {write_morphology(p.file_id, morphology_rows)}")
         if drops is not None:
             print(f"  {write_droplets(p.file_id, droplets_rows)}")
+        if wid is not None:
+            print(f"  {write_widths(p.file_id, widths_rows)}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

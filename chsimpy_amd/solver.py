@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, components, morphology, mport, spectrum
+from . import _lib, components, distance, morphology, mport, spectrum
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -188,6 +188,21 @@ class Solver:
         self._push_edited_U()
         words, tab, lab = eng.components_look(t, conn, code, table, labels)
         return components.Components(words, self.params.N, t, conn, code, table=tab, labels=lab, delx=self.solution.delx)
+
+    def distance(self, threshold=None, side='below', hist=True, map=False):
+        """The exact Euclidean distance transform of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): how wide the domains are in real space -- the widest point, the mean squared half-width,
+        the histogram of local radii -- a self-contained `distance.Distance` from one look on the device between two
+        calls, which the run does not notice.  ``side='below'`` is the foreground of `morphology`, ``'above'`` its
+        complement; the histogram and the N x N map of squared distances are fetched in this call when asked for (without
+        ``map=True`` nothing N x N leaves the device).  A field the host edited is pushed first, as solve_or_resume
+        does.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        code = distance.side_code(side)
+        eng = self._get_engine()
+        self._push_edited_U()
+        words, hi, d2 = eng.distance_look(t, code, hist, map)
+        return distance.Distance(words, self.params.N, t, code, hist=hi, d2=d2, delx=self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

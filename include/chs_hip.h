@@ -334,6 +334,48 @@ int chs_components_last_ms(chs_handle h, double* ms);
 /* The extents of the tile a workgroup labels in LDS (what the tests size their fields by). */
 int chs_components_tile(int32_t* rows, int32_t* cols);
 
+/* ---- Distance transform of the thresholded field: domain widths, widest point, histogram ----
+ * Foreground X: exactly that of chs_components.  side = CHS_CC_BELOW: X[i][j] = ((double)U[i][j] < t), a NaN pixel and
+ * a pixel equal to t are background; side = CHS_CC_ABOVE: the complement inside the grid.  t is finite.
+ * Squared distance: D2[i][j], an int32, is 0 for a background pixel and, for a foreground pixel, the minimum over all
+ * background pixels (k, l) OF THE GRID of (i-k)^2 + (j-l)^2: the exact squared Euclidean distance to the nearest
+ * background pixel.  No wrap-around, and the box walls are not background (scipy.ndimage.distance_transform_edt's
+ * convention).  A grid without any background pixel has D2 = CHS_DT_INF = 1 << 30 everywhere: above 2 (N-1)^2 for
+ * every N a handle takes, and d^2 + CHS_DT_INF stays inside int32.
+ * Radius bin of a foreground pixel: k = isqrt(D2), k^2 <= D2 < (k+1)^2, computed in integers.
+ * Histogram: hist[k], int64, the foreground pixels in bin k; its length is chs_distance_bins(N) = isqrt(2 (N-1)^2) + 1;
+ * CHS_DT_INF pixels are in no bin.
+ * Summary: CHS_DT_WORDS int64 words at the indices below:
+ *   FG           foreground pixels
+ *   D2MAX        the largest D2 over the foreground pixels with D2 < CHS_DT_INF, 0 if there is none
+ *   D2MAX_FIRST  the smallest linear index i*N + j attaining D2MAX; -1 if FG == 0 or every foreground pixel is INF
+ *                (the maximum of (D2, -index), a total order: every reduction order gives the same words)
+ *   SUMD2        the sum of D2 over those same pixels
+ *   NINF         pixels with D2 == CHS_DT_INF: 0 or N^2
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone and writes buffers of its own (allocated at the first look, freed with the handle), so the run does not notice
+ * it; everything is integer, so two looks return the same bits.  Histogram and map of the last look stay available
+ * until the next look.  Every loop of the kernels has a cap it cannot reach; one that reaches it makes the look return
+ * CHS_ECHECK and chs_last_error names it.  CHS_EINVAL for a null argument, a threshold that is not finite, a side other
+ * than 0 or 1, or nbins != chs_distance_bins(N) (the message gives the expected value); CHS_ESTATE for _hist / _map /
+ * _last_ms without a look. */
+#define CHS_DT_WORDS 5
+#define CHS_DT_FG 0
+#define CHS_DT_D2MAX 1
+#define CHS_DT_D2MAX_FIRST 2
+#define CHS_DT_SUMD2 3
+#define CHS_DT_NINF 4
+#define CHS_DT_INF (1 << 30)
+int32_t chs_distance_bins(int32_t N);   /* 0 for N < 1 */
+int chs_distance(chs_handle h, double threshold, int32_t side, int64_t out[CHS_DT_WORDS]);
+int chs_distance_hist(chs_handle h, int32_t nbins, int64_t* out);   /* [nbins] of the last look */
+int chs_distance_map(chs_handle h, int32_t* out);                   /* [N][N] D2 of the last look */
+/* Device time (ms, HIP events) of the handle's last look, first launch to last. */
+int chs_distance_last_ms(chs_handle h, double* ms);
+/* The kernels' geometry (what the tests size their fields by): the rows of a band of the vertical pass, and the
+ * consecutive pixels of a row that one wavefront pass of the horizontal pass covers. */
+int chs_distance_tile(int32_t* band_rows, int32_t* row_chunk);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -411,6 +453,12 @@ int chs_batch_morphology(chs_batch b, int32_t member, const double* threshold, i
 int chs_batch_components(chs_batch b, int32_t member, double threshold, int32_t connectivity, int32_t side, int64_t out[CHS_CC_WORDS]);
 int chs_batch_components_table(chs_batch b, int64_t rows, int32_t* out);
 int chs_batch_components_labels(chs_batch b, int32_t* out);
+/* chs_distance of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of buffers for the batch,
+ * so histogram and map are those of the batch's last look, whichever member it was.  Words, histogram and map are those
+ * of the member's single handle on the same field.  The members' states, fields and records stay untouched. */
+int chs_batch_distance(chs_batch b, int32_t member, double threshold, int32_t side, int64_t out[CHS_DT_WORDS]);
+int chs_batch_distance_hist(chs_batch b, int32_t nbins, int64_t* out);
+int chs_batch_distance_map(chs_batch b, int32_t* out);
 
 #ifdef __cplusplus
 }
