@@ -27,6 +27,7 @@ CHS_CC_COLS = 6               # int32 columns of its table: first, area, imin, i
 CHS_CC_BELOW, CHS_CC_ABOVE = 0, 1
 CHS_DT_WORDS = 5              # int64 words of chs_distance: fg, d2max, d2max_first, sumd2, ninf
 CHS_DT_INF = 1 << 30          # D2 of every pixel of a grid without background
+CHS_CH_WORDS = 24             # int64 words of chs_chords: six per (phase, direction)
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -48,6 +49,8 @@ SYMBOLS = (
     'chs_batch_components', 'chs_batch_components_table', 'chs_batch_components_labels',
     'chs_distance_bins', 'chs_distance', 'chs_distance_hist', 'chs_distance_map', 'chs_distance_last_ms', 'chs_distance_tile',
     'chs_batch_distance', 'chs_batch_distance_hist', 'chs_batch_distance_map',
+    'chs_chords_bins', 'chs_chords', 'chs_chords_hist', 'chs_chords_last_ms', 'chs_chords_tile',
+    'chs_batch_chords', 'chs_batch_chords_hist',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -190,6 +193,14 @@ def load():
     lib.chs_batch_distance.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, i64p]
     lib.chs_batch_distance_hist.argtypes = [vp, C.c_int32, i64p]
     lib.chs_batch_distance_map.argtypes = [vp, i32p]
+    lib.chs_chords_bins.argtypes = [C.c_int32]
+    lib.chs_chords_bins.restype = C.c_int32
+    lib.chs_chords.argtypes = [vp, C.c_double, i64p]
+    lib.chs_chords_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_chords_last_ms.argtypes = [vp, dp]
+    lib.chs_chords_tile.argtypes = [i32p, i32p, i32p]
+    lib.chs_batch_chords.argtypes = [vp, C.c_int32, C.c_double, i64p]
+    lib.chs_batch_chords_hist.argtypes = [vp, C.c_int32, i64p]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -241,6 +252,21 @@ def distance_tile():
 def distance_bins(N):
     """The length of the histogram of chs_distance at grid size N (chs_distance_bins)."""
     return int(load().chs_distance_bins(int(N)))
+
+
+def chords_tile():
+    """(word_bits, lines_per_group, local_bins) of the kernels of chs_chords (chs_chords_tile): the pixels of a line in one
+    word, the lines of a workgroup of the walk, and the lengths below which a chord goes to the workgroup's histogram."""
+    w, g, b = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = load().chs_chords_tile(C.byref(w), C.byref(g), C.byref(b))
+    if rc != CHS_OK:
+        raise EngineError(f"chs_chords_tile failed ({rc})")
+    return int(w.value), int(g.value), int(b.value)
+
+
+def chords_bins(N):
+    """The bins of each of the eight histograms of chs_chords at grid size N (chs_chords_bins)."""
+    return int(load().chs_chords_bins(int(N)))
 
 
 def __getattr__(name):
@@ -455,6 +481,31 @@ class Engine:
         self._check(self.lib.chs_distance_last_ms(self._h, C.byref(ms)), 'chs_distance_last_ms')
         return float(ms.value)
 
+    def chords(self, threshold):
+        """The 24 int64 summary words of the chord lengths of the field the device holds (chs_chords;
+        chsimpy_amd/chords.py names them).  The histograms of this look: `chords_hist`."""
+        out = np.empty(CHS_CH_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_chords(self._h, float(threshold), _i64ptr(out)), 'chs_chords')
+        return out
+
+    def chords_hist(self):
+        """int64 [2][2][2][chs_chords_bins(N)] of the last look: the chords by phase, direction, class and length."""
+        nb = int(self.lib.chs_chords_bins(self.N))
+        out = np.empty((2, 2, 2, nb), dtype=np.int64)
+        self._check(self.lib.chs_chords_hist(self._h, nb, _i64ptr(out)), 'chs_chords_hist')
+        return out
+
+    def chords_look(self, threshold, hist=True):
+        """One look with what belongs to it: (words, histograms or None)."""
+        words = self.chords(threshold)
+        return words, (self.chords_hist() if hist else None)
+
+    def chords_ms(self):
+        """Device time (ms) of the last `chords`."""
+        ms = C.c_double(0.0)
+        self._check(self.lib.chs_chords_last_ms(self._h, C.byref(ms)), 'chs_chords_last_ms')
+        return float(ms.value)
+
     def components_ms(self):
         """Device time (ms) of the last `components`."""
         ms = C.c_double(0.0)
@@ -639,6 +690,23 @@ class Batch:
     def distance_look(self, member, threshold, side, hist=True, map=False):
         words = self.distance(member, threshold, side)
         return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
+
+    def chords(self, member, threshold):
+        """`Engine.chords` of one member (chs_batch_chords): the batch has one set of buffers, so the histograms are
+        those of its last look."""
+        out = np.empty(CHS_CH_WORDS, dtype=np.int64)
+        self._check(self.lib.chs_batch_chords(self._h, int(member), float(threshold), _i64ptr(out)), 'chs_batch_chords')
+        return out
+
+    def chords_hist(self):
+        nb = int(self.lib.chs_chords_bins(self.N))
+        out = np.empty((2, 2, 2, nb), dtype=np.int64)
+        self._check(self.lib.chs_batch_chords_hist(self._h, nb, _i64ptr(out)), 'chs_batch_chords_hist')
+        return out
+
+    def chords_look(self, member, threshold, hist=True):
+        words = self.chords(member, threshold)
+        return words, (self.chords_hist() if hist else None)
 
     def get_state(self, member):
         s = chs_state()

@@ -136,6 +136,12 @@ class _Member:
     def distance_look(self, threshold, side, hist=True, map=False):
         return self._b.distance_look(self._m, threshold, side, hist, map)
 
+    def chords(self, threshold):
+        return self._b.chords(self._m, threshold)
+
+    def chords_look(self, threshold, hist=True):
+        return self._b.chords_look(self._m, threshold, hist)
+
     def close(self):
         pass  # (the batch owns the device state)
 
@@ -317,6 +323,17 @@ class BatchSolver:
         if member is not None:
             return self.solvers[member].distance(ts[member], side, hist, map)
         return [s.distance(t, side, hist, map) for s, t in zip(self.solvers, ts)]
+
+    def chords(self, member=None, threshold=None, hist=True):
+        """The members' chord lengths (`Solver.chords`): a list of one `chords.Chords` per member, looked at member by
+        member on the batch's stream with the batch's one set of buffers, or the one of ``member``.  ``threshold``: one
+        value for all, one per member, or None for every member's own ``params.threshold``.  The members' runs do not
+        notice the looks."""
+        self._get_batch()
+        ts = self._member_thresholds(threshold)
+        if member is not None:
+            return self.solvers[member].chords(ts[member], hist)
+        return [s.chords(t, hist) for s, t in zip(self.solvers, ts)]
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

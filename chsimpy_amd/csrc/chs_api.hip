@@ -89,6 +89,7 @@ static void free_engine(Engine* E) {
   chs_morph_free(&E->morph);
   chs_cc_free(&E->cc);
   chs_dt_free(&E->dt);
+  chs_ch_free(&E->ch);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
   hipFree(E->dT1); hipFree(E->dHat);
   if (E->dHat2) hipFree(E->dHat2);
@@ -191,6 +192,7 @@ static int rearm(Engine* E, const chs_consts* c) {
   chs_morph_forget(E->morph);   // (a handle from the pool has had no look: chs_morphology_last_ms)
   chs_cc_forget(E->cc);
   chs_dt_forget(E->dt);
+  chs_ch_forget(E->ch);
   read_env_hooks(E);
   if (E->engine == CHS_ENGINE_FAST) return chs_fast_rearm(E);
   return CHS_OK;

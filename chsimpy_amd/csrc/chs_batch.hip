@@ -164,6 +164,7 @@ struct Batch {
   void* morph = nullptr;         // chs_batch_morphology of all members: its buffers (chs_morphology.hip), at the first look
   void* cc = nullptr;            // chs_batch_components: the batch's one set of buffers (chs_components.hip), at the first look
   void* dt = nullptr;            // chs_batch_distance: the batch's one set of buffers (chs_distance.hip), at the first look
+  void* ch = nullptr;            // chs_batch_chords: the batch's one set of buffers (chs_chords.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -183,6 +184,7 @@ void batch_free(Batch* b) {
   chs_morph_free(&b->morph);
   chs_cc_free(&b->cc);
   chs_dt_free(&b->dt);
+  chs_ch_free(&b->ch);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -842,4 +844,18 @@ extern "C" int chs_batch_distance_map(chs_batch h, int32_t* out) {
   Batch* b = as_batch(h);
   if (!b) return bad("chs_batch_distance_map: null handle");
   return chs_dt_map(b->dt, b->m[0]->hc.device, b->stream, out, "chs_batch_distance_map");
+}
+
+// The chord lengths of one member: the single handle's look on the batch's stream, with the batch's one set of buffers.
+extern "C" int chs_batch_chords(chs_batch h, int32_t member, double threshold, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_chords: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_chords: no such member");
+  return chs_ch_look(b->m[(size_t)member], b->stream, &b->ch, threshold, out, "chs_batch_chords");
+}
+
+extern "C" int chs_batch_chords_hist(chs_batch h, int32_t nbins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_chords_hist: null handle");
+  return chs_ch_hist(b->ch, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_chords_hist");
 }

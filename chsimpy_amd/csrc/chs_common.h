@@ -252,6 +252,7 @@ struct Engine {
   void* morph = nullptr;       // morphology: tile partials, result, events (chs_morphology.hip), at the first look
   void* cc = nullptr;          // connected components: labels, numbers, table, result, events (chs_components.hip), at the first look
   void* dt = nullptr;          // distance transform: band masks, carries, D2, histogram, result, events (chs_distance.hip), at the first look
+  void* ch = nullptr;          // chord lengths: bit planes, histograms, result, events (chs_chords.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -431,3 +432,12 @@ int chs_dt_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* ou
 int chs_dt_map(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
 void chs_dt_free(void** buf);
 void chs_dt_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- chord lengths (chs_chords.hip) -------------------------------------------
+// The chord lengths of both phases of E's field thresholded at `threshold`, along rows and columns (DESIGN.md section
+// 3f), on stream `s` with the buffer set *buf (the handle's own, or the batch's one set), allocated here at the first
+// look: out[CHS_CH_WORDS].  The histograms of the last look of a buffer set: chs_ch_hist.
+int chs_ch_look(Engine* E, hipStream_t s, void** buf, double threshold, int64_t* out, const char* who);
+int chs_ch_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
+void chs_ch_free(void** buf);
+void chs_ch_forget(void* buf);   // the buffers stay, the last look goes

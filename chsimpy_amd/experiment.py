@@ -162,14 +162,29 @@ def _widths_of(solver):
     return (below.threshold,) + _widths_side(below) + _widths_side(above)
 
 
+def _chords_of(solver):
+    """(threshold, then count, mean, mean_weighted, max, cut for below/above x rows/cols) of a member's final field: one
+    look behind its run, the summary words alone; NaN where a phase has no inner chord along a direction."""
+    from . import chords as ch
+    nan = float('nan')
+    co = solver.chords(hist=False)
+    row = (co.threshold,)
+    for p in ch.PHASES:
+        for d in ch.DIRECTIONS:
+            k = co.count(p, d)
+            row += (k, co.mean(p, d) if k else nan, co.mean_weighted(p, d) if k else nan, co.word('max_inner', p, d), co.cut(p, d))
+    return row
+
+
 def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None,
-                       morphology=None, droplets=None, droplets_connectivity=4, widths=None):
+                       morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None):
     """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains`` (a dict): the
     member's domain size, measured on the device behind its run, goes to ``domains[run_id]``; ``morphology`` (a dict):
     likewise the morphology of its final field at ``params.threshold``; ``droplets`` (a dict): likewise its connected
     components on both sides of that threshold (summary-only looks, ``droplets_connectivity`` 4 or 8); ``widths`` (a
     dict): likewise the distance transform on both sides of it (widest point, mean squared radius, radius-bin mean and
-    quantiles)."""
+    quantiles); ``chords`` (a dict): likewise the chord lengths of both phases along rows and columns (one summary-only
+    look)."""
     from .simulator import Simulator
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
@@ -183,6 +198,8 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
             droplets[run_id] = _droplets_of(simulator.solver, droplets_connectivity)
         if widths is not None:
             widths[run_id] = _widths_of(simulator.solver)
+        if chords is not None:
+            chords[run_id] = _chords_of(simulator.solver)
         simulator.export()
         rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
@@ -192,12 +209,12 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
 
 
 def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None,
-                  morphology=None, droplets=None, droplets_connectivity=4, widths=None):
+                  morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
     members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``,
-    ``morphology``: as in run_experiment_gpu, each from one device pass over the group; ``droplets``, ``widths``: as
-    there, member by member on the batch's stream."""
+    ``morphology``: as in run_experiment_gpu, each from one device pass over the group; ``droplets``, ``widths``, ``chords``:
+    as there, member by member on the batch's stream."""
     from .batch import BatchSolver
     from .simulator import Simulator
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
@@ -217,6 +234,9 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
         if widths is not None:
             for i, s in zip(run_ids, bs.solvers):
                 widths[i] = _widths_of(s)
+        if chords is not None:
+            for i, s in zip(run_ids, bs.solvers):
+                chords[i] = _chords_of(s)
         recs = []
         for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
             # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
@@ -363,6 +383,41 @@ def write_widths(file_id, rows):
     return name
 
 
+CHORDS_COLS = ('id', 'threshold') + tuple(f"{k}_{phase}_{d}" for phase in ('below', 'above') for d in ('rows', 'cols')
+                                          for k in ('count', 'mean', 'mean_weighted', 'max', 'cut'))
+
+
+def gather_chords(local, nr_items, rank, world, dist=None, device='cpu'):
+    """The members' CHORDS_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the twenty-one
+    values behind the id.  One all_gather of a float64 block per rank, as gather_widths (the counts are integers below
+    2^53: exact in float64; a phase without an inner chord has NaN there, which only the id column is tested for)."""
+    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
+    if world == 1 or dist is None:
+        return rows
+    import torch
+    per = (nr_items + world - 1) // world
+    buf = torch.full((per, len(CHORDS_COLS)), float('nan'), dtype=torch.float64, device=device)
+    for k, row in enumerate(rows):
+        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
+    out = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(out, buf)
+    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
+    return sorted((int(r[0]),) + r[1:] for r in got)
+
+
+def write_chords(file_id, rows):
+    """``<file_id>-chords.csv``: CHORDS_COLS per member (--chords), the counts and the longest chords as integers, the
+    floats written so that they read back exactly."""
+    name = f"{file_id}-chords.csv"
+    with open(name, 'w') as f:
+        f.write(','.join(CHORDS_COLS) + "\n")
+        for row in rows:
+            i, t, groups = row[0], row[1], [row[2 + 5 * k:7 + 5 * k] for k in range(4)]
+            f.write(f"{int(i)},{float(t)!r}" + ''.join(
+                f",{int(n)},{float(m)!r},{float(mw)!r},{int(mx)},{int(cut)}" for n, m, mw, mx, cut in groups) + "\n")
+    return name
+
+
 def write_morphology(file_id, rows):
     """``<file_id>-morphology.csv``: MORPHOLOGY_COLS per member (--morphology), the counts as integers, the two floats
     written so that they read back exactly."""
@@ -410,7 +465,7 @@ def write_results(file_id, records):
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
                  concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None, morphology=None,
-                 droplets=None, droplets_connectivity=4, widths=None):
+                 droplets=None, droplets_connectivity=4, widths=None, chords=None):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -444,7 +499,11 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
 
     ``widths`` (a dict, with the default run functions): likewise the distance transform of every member's final field
     on both sides of its ``params.threshold`` -- foreground, widest point, mean squared radius, radius-bin mean and
-    quantiles (chsimpy_amd/distance.py) -- in ``widths[run_id]`` (gather_widths)."""
+    quantiles (chsimpy_amd/distance.py) -- in ``widths[run_id]`` (gather_widths).
+
+    ``chords`` (a dict, with the default run functions): likewise the chord lengths of both phases of every member's
+    final field along rows and columns -- count, mean, weighted mean, longest inner chord and the chords at a wall
+    (chsimpy_amd/chords.py) -- in ``chords[run_id]`` (gather_chords)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
     dom = {} if domains is None else {'domains': domains}   # (the run functions are called as ever without it)
     if morphology is not None:
@@ -453,6 +512,8 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
         dom['droplets'], dom['droplets_connectivity'] = droplets, int(droplets_connectivity)
     if widths is not None:
         dom['widths'] = widths
+    if chords is not None:
+        dom['chords'] = chords
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
             return run_experiment_gpu(run_id, p, rv, al, U_init, **dom)
@@ -553,6 +614,10 @@ def main(argv=None):
     ap.add_argument('--widths', action='store_true', help='measure the exact Euclidean distance transform of every member\'s '
                     'final field on the device behind its run, on both sides of the threshold: <id>-widths.csv with id, '
                     'threshold, and fg, r_max, r2_mean, r_floor_mean, q50, q90 (radius-bin quantiles) below and above')
+    ap.add_argument('--chords', action='store_true', help='measure the chord lengths (linear intercepts) of both phases of '
+                    'every member\'s final field on the device behind its run, along rows and columns: <id>-chords.csv with '
+                    'id, threshold, and count, mean, mean_weighted, max (inner chords), cut (chords at a wall) for '
+                    'below/above x rows/cols')
     ap.add_argument('--droplets-connectivity', type=int, choices=(4, 8), default=4, help='the connectivity of --droplets')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
@@ -608,13 +673,15 @@ def main(argv=None):
     morph = {} if a.morphology else None
     drops = {} if a.droplets else None
     wid = {} if a.widths else None
+    cho = {} if a.chords else None
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
                            batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
                            queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains,
                            **({} if morph is None else {'morphology': morph}),
                            **({} if drops is None else {'droplets': drops, 'droplets_connectivity': a.droplets_connectivity}),
-                           **({} if wid is None else {'widths': wid}))
+                           **({} if wid is None else {'widths': wid}),
+                           **({} if cho is None else {'chords': cho}))
     if domains is not None:
         if a.dry_run:   # (members without device work: a function of the run id, as their records are)
             nr = make_rand_values(ep)[2]
@@ -639,6 +706,13 @@ def main(argv=None):
                        p.N * p.N - (i + 1), float(i + 2), 0.5 * (i + 2) ** 2, 0.5 * (i + 2), (i + 2) // 2, i + 2)
                    for i in my_run_ids(nr, rank, world)}
         widths_rows = gather_widths(wid, nr, rank, world, dist, device)
+    if cho is not None:
+        nr = make_rand_values(ep)[2]
+        if a.dry_run:   # (made up from the run id, as above: i + 1 inner chords of 2 and 4 pixels below along the rows, ...)
+            cho = {i: (float(p.threshold), i + 1, 3.0, 10.0 / 3.0, 4, 1, i + 2, 1.5, 1.75, 2, 0,
+                       i + 3, float(i + 2), i + 2.5, 2 * i + 4, p.N, i + 4, 0.1 * (i + 1), 1.0 / (i + 3), i + 5, p.N + 1)
+                   for i in my_run_ids(nr, rank, world)}
+        chords_rows = gather_chords(cho, nr, rank, world, dist, device)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)
@@ -654,6 +728,8 @@ def main(argv=None):
             print(f"  {write_droplets(p.file_id, droplets_rows)}")
         if wid is not None:
             print(f"  {write_widths(p.file_id, widths_rows)}")
+        if cho is not None:
+            print(f"  {write_chords(p.file_id, chords_rows)}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, components, distance, morphology, mport, spectrum
+from . import _lib, chords, components, distance, morphology, mport, spectrum
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -203,6 +203,20 @@ class Solver:
         self._push_edited_U()
         words, hi, d2 = eng.distance_look(t, code, hist, map)
         return distance.Distance(words, self.params.N, t, code, hist=hi, d2=d2, delx=self.solution.delx)
+
+    def chords(self, threshold=None, hist=True):
+        """The chord lengths (linear intercepts) of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): the segments the rows and the columns cut out of each phase -- count, mean, weighted
+        mean and longest chord per phase and direction, the anisotropy, and with the histograms the quantiles and the
+        lineal-path function -- a self-contained `chords.Chords` from one look on the device between two calls, which
+        the run does not notice.  One look gives both phases and both directions; the histograms (8 (N + 1) integers)
+        are fetched in this call unless ``hist=False``; nothing N x N leaves the device.  A field the host edited is
+        pushed first, as solve_or_resume does.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        eng = self._get_engine()
+        self._push_edited_U()
+        words, hi = eng.chords_look(t, hist)
+        return chords.Chords(words, self.params.N, t, hist=hi, delx=self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

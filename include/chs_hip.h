@@ -376,6 +376,50 @@ int chs_distance_last_ms(chs_handle h, double* ms);
  * consecutive pixels of a row that one wavefront pass of the horizontal pass covers. */
 int chs_distance_tile(int32_t* band_rows, int32_t* row_chunk);
 
+/* ---- Chord lengths (linear intercepts) of both phases, along rows and columns ----
+ * For the N x N field U and a finite threshold t:
+ * Phase 0 is the foreground of chs_components with CHS_CC_BELOW: X[i][j] = ((double)U[i][j] < t); a NaN pixel and a
+ * pixel equal to t are not phase 0.  Phase 1 is the complement inside the grid.  There is no side argument: one look
+ * gives both.
+ * Direction CHS_CH_ROWS = 0: the lines are the rows, a chord runs along j.  Direction CHS_CH_COLS = 1: the lines are the
+ * columns, a chord runs along i.
+ * A chord is a maximal run of consecutive pixels of one phase within one line; its length c is in [1, N].  No
+ * wrap-around.
+ * Class CHS_CH_INNER = 0: both ends are bounded by the other phase.  Class CHS_CH_CUT = 1: the chord touches a wall: it
+ * begins at index 0, or ends at N-1, or both; a run of length N is one cut chord.
+ * Histogram: hist[phase][dir][cls][c], int64, 2*2*2*(N+1) entries in that order: the chords of length c.  Bin 0 is
+ * always 0.  chs_chords_bins(N) = N + 1, and 0 for N < 1.
+ * Summary: CHS_CH_WORDS = 24 int64 words, six per (phase, dir) in the order phase, dir, at the indices below: N_INNER,
+ * SUM_INNER, SUM2_INNER, MAX_INNER, N_CUT, SUM_CUT -- the count, the sum of c, the sum of c^2 and the largest c of the
+ * class (0 without one).  The largest value is N^3, inside int64 for every N a handle takes.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone and writes buffers of its own (allocated at the first look, freed with the handle), so the run does not notice
+ * it; everything is integer, so two looks return the same bits.  The histogram of the last look stays available until
+ * the next look.  The look checks itself: per direction the chords of both phases and classes add up to N^2 pixels and
+ * the cut chords of both phases are N to 2 N, and every loop of the kernels has a cap it cannot reach; a violation makes
+ * the look return CHS_ECHECK and chs_last_error names it.  CHS_EINVAL for a null argument, a threshold that is not
+ * finite or nbins != chs_chords_bins(N) (the message gives the expected value); CHS_ESTATE for _hist / _last_ms
+ * without a look. */
+#define CHS_CH_WORDS 24
+#define CHS_CH_ROWS 0
+#define CHS_CH_COLS 1
+#define CHS_CH_INNER 0
+#define CHS_CH_CUT 1
+#define CHS_CH_N_INNER 0
+#define CHS_CH_SUM_INNER 1
+#define CHS_CH_SUM2_INNER 2
+#define CHS_CH_MAX_INNER 3
+#define CHS_CH_N_CUT 4
+#define CHS_CH_SUM_CUT 5
+int32_t chs_chords_bins(int32_t N);   /* 0 for N < 1 */
+int chs_chords(chs_handle h, double threshold, int64_t out[CHS_CH_WORDS]);
+int chs_chords_hist(chs_handle h, int32_t nbins, int64_t* out);        /* [2][2][2][nbins] of the last look */
+/* Device time (ms, HIP events) of the handle's last look, first launch to last. */
+int chs_chords_last_ms(chs_handle h, double* ms);
+/* The kernels' geometry (what the tests size their fields by): the pixels of a line in one word, the lines of a
+ * workgroup of the walk, and the lengths below which a chord goes to the workgroup's histogram. */
+int chs_chords_tile(int32_t* word_bits, int32_t* lines_per_group, int32_t* local_bins);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -459,6 +503,11 @@ int chs_batch_components_labels(chs_batch b, int32_t* out);
 int chs_batch_distance(chs_batch b, int32_t member, double threshold, int32_t side, int64_t out[CHS_DT_WORDS]);
 int chs_batch_distance_hist(chs_batch b, int32_t nbins, int64_t* out);
 int chs_batch_distance_map(chs_batch b, int32_t* out);
+/* chs_chords of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of buffers for the batch,
+ * so the histogram is that of the batch's last look, whichever member it was.  Words and histogram are those of the
+ * member's single handle on the same field.  The members' states, fields and records stay untouched. */
+int chs_batch_chords(chs_batch b, int32_t member, double threshold, int64_t out[CHS_CH_WORDS]);
+int chs_batch_chords_hist(chs_batch b, int32_t nbins, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,313 @@
+"""GPU tests (``-m gpu``) of the chord lengths of the thresholded field on the device (chs_chords / chs_batch_chords,
+chsimpy_amd/csrc/chs_chords.hip).
+
+Reference: the numpy model ``chords.chord_histograms`` (tests/test_chords_host.py holds it against a brute-force walk) on
+the phase-0 image of the field as downloaded with ``get_U`` -- the exact values the device holds, also for fp32 -- and,
+for the hand-made patterns, the chords in closed form.  Everything is integer: every comparison is for equality of the 24
+words and of the eight histograms.
+
+``W, G, L`` are the pixels of a line in one word, the lines of a workgroup of the walk and the lengths below which a
+chord goes to the workgroup's histogram (``_lib.chords_tile()``); the pattern sizes are the smallest at which each phase
+can still go wrong."""
+import math
+
+import numpy as np
+import pytest
+
+import chsimpy_amd
+from chsimpy_amd import _lib, chords
+from chsimpy_amd.batch import BatchSolver
+from gpu_helpers import make
+import test_gpu_spectrum as tgs
+import test_chords_host as host
+import test_morphology_host as mh
+
+pytestmark = pytest.mark.gpu
+
+T = host.T
+TILE = host.tile_from_source()        # (the library's own is checked against it below)
+W, G, L = TILE
+
+
+def engine_of(N, engine, dtype='float64'):
+    s = chsimpy_amd.Solver(make(N, 2, engine, dtype=dtype))
+    eng = s._get_engine()
+    assert eng.engine == engine
+    return s, eng
+
+
+def dev_look(eng, t, hist=True):
+    words, hi = eng.chords_look(t, hist)
+    return chords.Chords(words, eng.N, t, hist=hi)
+
+
+def phase0_of(Ud, t):
+    return np.nan_to_num(np.asarray(Ud, dtype=np.float64), nan=np.inf) < t
+
+
+# ---------------------------------------------------------------------------
+# 1. patterns
+# ---------------------------------------------------------------------------
+def test_the_tile_is_the_sources(gpu):
+    assert _lib.chords_tile() == TILE
+    assert host.tile_sizes(TILE) == sorted({8, W - 1, W, W + 1, 2 * W + 1, 2 * W + 2, G + 1, L + 1})
+
+
+def _pattern_look(eng, check_upload=False):
+    def look(U, t):
+        eng.set_U(U)
+        if check_upload:
+            assert np.array_equal(eng.get_U() < t, U < t)
+        return dev_look(eng, t)
+    return look
+
+
+@pytest.mark.parametrize("N", host.tile_sizes(TILE))
+def test_patterns_on_the_device(gpu, N):
+    s, eng = engine_of(N, 'chirp')
+    look = _pattern_look(eng)
+    names = []
+    for name, U, want in host.patterns(N, TILE):
+        host.check_pattern(look, name, U, want, N)
+        names.append(name)
+    assert 'checkerboard' in names and 'all-phase-0' in names and 'long-chords-along-cols' in names
+    if N == L + 1:                                       # the chords that go past the workgroup's histogram
+        assert 'three-words-from-bit-30-along-cols' in names and 'six-words-from-bit-10-along-rows' in names
+        co = look(np.full((N, N), host.FG), T)
+        assert co.hist[0, :, host.CUT, L + 1].tolist() == [N, N] and int(co.hist.sum()) == 2 * N
+    for name, U, t, _ in mh.hand_made(N):               # the threshold, NaN and one-ulp fields
+        host.check_look(look(U, t), phase0_of(U, t), f"{name} N={N}")
+    s.close(fetch_U=False)
+
+
+@pytest.mark.parametrize("N", [2 * W + 1, 2 * W + 4])
+def test_patterns_on_the_device_fp32(gpu, N):
+    """An odd N and a multiple of four: the mask kernel loads element by element at every N."""
+    s, eng = engine_of(N, 'chirp', 'float32')
+    look = _pattern_look(eng, check_upload=True)
+    for name, U, want in host.patterns(N, TILE):
+        host.check_pattern(look, name, U, want, N)
+    s.close(fetch_U=False)
+
+
+# ---------------------------------------------------------------------------
+# 2. random fields: both parities, every engine and element type
+# ---------------------------------------------------------------------------
+RANDOM_CASES = [(8, 'chirp', 'float64'), (100, 'chirp', 'float32'), (129, 'chirp', 'float32'), (512, 'fast', 'float32'),
+                (513, 'chirp', 'float64'), (100, 'direct', 'float64')]
+
+
+@pytest.mark.parametrize("N,engine,dtype", RANDOM_CASES, ids=[f"N{c[0]}-{c[1]}-{c[2]}" for c in RANDOM_CASES])
+def test_random_fields(gpu, N, engine, dtype):
+    s, eng = engine_of(N, engine, dtype)
+    rng = np.random.default_rng(17 * N + len(engine))
+    for density in (0.3, 0.6, 0.95):
+        U = mh.field_of(rng.random((N, N)) < density)
+        k = max(2, N // 16)
+        U[rng.integers(0, N, k), rng.integers(0, N, k)] = T     # a few pixels at the threshold: not phase 0
+        eng.set_U(U)
+        Ud = eng.get_U()
+        assert np.array_equal(Ud == T, U == T)
+        co = dev_look(eng, T)
+        host.check_look(co, phase0_of(Ud, T), f"N={N} {engine} {dtype} {density}")
+        assert 0 < co.n('below') < N * N
+        if N >= 100:                                             # (at N = 8 every chord of a phase may lie at a wall)
+            assert co.count('below', 'rows') > 0 and co.count('above', 'cols') > 0
+    assert eng.chords_ms() >= 0.0
+    s.close(fetch_U=False)
+
+
+# ---------------------------------------------------------------------------
+# 3. an evolved field; the other looks of the same handle
+# ---------------------------------------------------------------------------
+def test_an_evolved_field_against_the_model_and_the_other_looks(gpu):
+    """After 40 steps at N = 512 fp64 on the fast engine, thresholded at the field's median: the device equals the
+    model; perimeter and area are the morphology's, the area the distance transform's foreground; the centre line of
+    the largest inscribed disc is no longer than the longest chord."""
+    N, steps = 512, 40
+    s = tgs.solver(N, steps + 1, 'fast')
+    s.prepare()
+    sol = s.solve_or_resume()
+    assert s._engine.engine == 'fast' and sol.computed_steps == steps + 1
+    U = s._engine.get_U()
+    t = float(np.median(U))
+    co = s.chords(t)
+    host.check_look(co, phase0_of(U, t), f"evolved N={N}")
+    assert co.threshold == t and co.N == N and co.delx == sol.delx and co.hist is not None
+    mo = s.morphology(t)
+    assert co.perimeter('below') == mo.perimeter and co.n('below') == mo.n_A == s.distance(t).fg
+    assert 0 < co.n('below') < N * N
+    for phase in host.PHASES:
+        di = s.distance(t, side=phase)
+        assert di.fg == co.n(phase) and di.d2max >= 1
+        i, j = di.argmax
+        h = math.isqrt(di.d2max - 1)                     # every pixel nearer than r_max is the phase's: |offset| <= h
+        for d, at in (('rows', j), ('cols', i)):
+            assert min(at, h) + min(N - 1 - at, h) + 1 <= co.max_all(phase, d), (phase, d)
+            if h <= at <= N - 1 - h:                     # the disc's centre line lies inside the grid
+                assert 2 * di.r_max - 1 <= 2 * math.ceil(di.r_max) - 1 == 2 * h + 1 <= co.max_all(phase, d)
+            assert co.mean_phys(phase, d) == co.mean(phase, d) * sol.delx
+            assert 1 <= co.quantile(0.5, phase, d) <= co.quantile(0.9, phase, d) <= co.max(phase, d) <= co.max_all(phase, d)
+        assert co.lineal_path(phase, 'rows')[0] == co.n(phase) / (N * N) == co.lineal_path(phase, 'cols')[0]
+    bare = s.chords(t, hist=False)
+    assert bare.hist is None and np.array_equal(bare.words, co.words)
+    own = s.chords()                                     # params.threshold
+    assert own.threshold == s.params.threshold and own.n('below') == s.morphology().n_A and own.hist is not None
+    s.close(fetch_U=False)
+
+
+# ---------------------------------------------------------------------------
+# 4. determinism; a look changes nothing
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("N,engine", [(128, 'fast'), (100, 'chirp')])
+def test_two_looks_give_the_same_bits(gpu, N, engine):
+    s = tgs.solver(N, 8, engine)
+    s.prepare()
+    s.solve_or_resume(4)
+    t = float(np.median(s._engine.get_U()))
+    a, b = s.chords(t), s.chords(t)
+    assert a.count('below', 'rows') > 1 and np.array_equal(a.words, b.words) and np.array_equal(a.hist, b.hist)
+    s.close(fetch_U=False)
+
+
+OBSERVE_CASES = [c for c in tgs.OBSERVE_CASES if c[0] <= 128 and not c[4]]     # the fast and the chirp engine
+
+
+@pytest.mark.parametrize("N,engine,calls,seed,kw", OBSERVE_CASES, ids=[f"N{c[0]}-{c[1]}" for c in OBSERVE_CASES])
+def test_a_look_between_calls_does_not_change_the_run(gpu, N, engine, calls, seed, kw):
+    """Calls with chords() between them against the same calls with get_U() between them: all nine record columns, the
+    state and the final field, bit for bit."""
+    assert {c[1] for c in OBSERVE_CASES} == {'fast', 'chirp'}
+
+    def look(s):
+        s.chords()
+        s.chords(hist=False)
+    got, Ug = tgs._observed_run(N, engine, calls, look, seed, **kw)
+    ref, Ur = tgs._observed_run(N, engine, calls, lambda s: s._engine.get_U(), seed, **kw)
+    for (rg, sg), (rr, sr) in zip(got, ref):
+        assert rg.shape == rr.shape
+        for c in range(9):
+            assert np.array_equal(rg[:, c], rr[:, c]), c
+        assert sg == sr
+    assert got[-1][0].shape[0] == 1 + sum(calls) - (1 if seed is None else 0)
+    assert np.array_equal(Ug, Ur)
+
+
+# ---------------------------------------------------------------------------
+# 5. batches
+# ---------------------------------------------------------------------------
+def _same(a, b):
+    return np.array_equal(a.words, b.words) and np.array_equal(a.hist, b.hist)
+
+
+@pytest.mark.parametrize("N,engine", [(256, 'fast'), (136, 'chirp')])
+def test_batch_equals_the_single_solvers_and_leaves_the_members_alone(gpu, N, engine):
+    B = 3
+    ps = tgs._members(N, B, 100)                         # (three members with their own A0, A1 and seed)
+    for m, p in enumerate(ps):
+        p.threshold = p.XXX + 1e-3 * (m - 1)             # ... and their own threshold
+    ts = [p.threshold for p in ps]
+    bs = BatchSolver(ps)
+    bs.prepare()
+    assert bs._batch.engine == engine
+    bs.solve_or_resume(20)
+    cos = bs.chords()                                    # every member at its own threshold
+    assert len(cos) == B and [co.threshold for co in cos] == ts
+    fields = [s._engine.get_U() for s in bs.solvers]
+    for m in range(B):
+        host.check_look(cos[m], phase0_of(fields[m], ts[m]), f"member {m}")
+        assert _same(bs.chords(m), cos[m]), m                                   # member = m
+        assert _same(bs.solvers[m].chords(), cos[m]), m                         # through the member's Solver
+        assert 0 < cos[m].n('below') < N * N
+    assert not np.array_equal(cos[0].words, cos[1].words)
+    same = bs.chords(threshold=ts[1])                                            # one threshold for all
+    for m in range(B):
+        host.check_look(same[m], phase0_of(fields[m], ts[1]), f"member {m} at one threshold")
+    assert _same(bs.chords(2, threshold=ts), cos[2])
+    assert bs.chords(0, hist=False).hist is None
+    with pytest.raises(ValueError):
+        bs.chords(threshold=[0.5])
+    bs.solve_or_resume(5)
+    looked = tgs._batch_snap(bs)
+    bs.close(fetch_U=False)
+    for m, p in enumerate(ps):                           # the three single Solvers run the same way
+        s = chsimpy_amd.Solver(p)
+        s.rederive_hat = True
+        s.prepare()
+        s.solve_or_resume(20)
+        assert _same(s.chords(), cos[m]), m
+        s.close(fetch_U=False)
+    ref = BatchSolver(ps)                                # the members' next call without the looks
+    ref.prepare()
+    ref.solve_or_resume(20)
+    ref.solve_or_resume(5)
+    plain = tgs._batch_snap(ref)
+    ref.close(fetch_U=False)
+    for m in range(B):
+        assert np.array_equal(looked[m][0], plain[m][0]) and np.array_equal(looked[m][1], plain[m][1]), m
+        assert looked[m][2] == plain[m][2], m
+
+
+# ---------------------------------------------------------------------------
+# 6. errors
+# ---------------------------------------------------------------------------
+def test_errors(gpu):
+    N = 128
+    s = tgs.solver(N, 4, 'fast')
+    eng = s._get_engine()
+    nb = _lib.chords_bins(N)
+    assert nb == N + 1
+    out = np.zeros(_lib.CHS_CH_WORDS, dtype=np.int64)
+    hist = np.zeros(8 * (nb + 1) + 1, dtype=np.int64)
+    ms = np.zeros(1)
+    o, h = _lib._i64ptr(out), _lib._i64ptr(hist)
+    assert gpu.chs_chords(eng._h, 0.5, o) == _lib.CHS_ESTATE                                 # no field yet
+    for call in (lambda: gpu.chs_chords_hist(eng._h, nb, h), lambda: gpu.chs_chords_last_ms(eng._h, _lib._dptr(ms))):
+        assert call() == _lib.CHS_ESTATE                                                    # no look yet
+    with pytest.raises(AssertionError):
+        s.chords()
+    s.prepare()
+    for bad in (float('nan'), float('inf'), -float('inf')):
+        assert gpu.chs_chords(eng._h, bad, o) == _lib.CHS_EINVAL
+        assert 'finite' in gpu.chs_last_error().decode()
+    assert gpu.chs_chords(eng._h, 0.5, None) == _lib.CHS_EINVAL
+    assert gpu.chs_chords(None, 0.5, o) == _lib.CHS_EINVAL
+    assert gpu.chs_chords_hist(None, nb, h) == _lib.CHS_EINVAL
+    assert gpu.chs_chords_last_ms(eng._h, None) == _lib.CHS_EINVAL
+    assert gpu.chs_chords_last_ms(eng._h, _lib._dptr(ms)) == _lib.CHS_ESTATE                 # none of them was a look
+    assert gpu.chs_chords_hist(eng._h, nb, h) == _lib.CHS_ESTATE
+    t = float(np.median(eng.get_U()))
+    assert gpu.chs_chords(eng._h, t, o) == _lib.CHS_OK
+    assert out[0] > 0 and gpu.chs_chords_last_ms(eng._h, _lib._dptr(ms)) == _lib.CHS_OK and ms[0] >= 0.0
+    for bins in (nb - 1, nb + 1, 8 * nb, 0, -1):
+        assert gpu.chs_chords_hist(eng._h, bins, h) == _lib.CHS_EINVAL
+        assert f"expected {nb}" in gpu.chs_last_error().decode()
+    assert gpu.chs_chords_hist(eng._h, nb, None) == _lib.CHS_EINVAL
+    hist[8 * nb] = -7
+    assert gpu.chs_chords_hist(eng._h, nb, h) == _lib.CHS_OK
+    assert hist[8 * nb] == -7
+    assert np.array_equal(chords.summary_of(hist[:8 * nb].reshape(2, 2, 2, nb)), out)
+    with pytest.raises(_lib.EngineError):
+        s.chords(float('nan'))
+    s.close(fetch_U=False)
+
+    bs = BatchSolver(tgs._members(128, 2, 10))
+    b = bs._get_batch()
+    assert gpu.chs_batch_chords(b._h, 0, 0.5, o) == _lib.CHS_ESTATE                          # no fields yet
+    assert gpu.chs_batch_chords_hist(b._h, nb, h) == _lib.CHS_ESTATE
+    bs.prepare()
+    for member in (2, -1, -2, 65536):
+        assert gpu.chs_batch_chords(b._h, member, 0.5, o) == _lib.CHS_EINVAL, member
+    assert gpu.chs_batch_chords(b._h, 1, float('nan'), o) == _lib.CHS_EINVAL
+    assert gpu.chs_batch_chords(b._h, 1, 0.5, None) == _lib.CHS_EINVAL
+    assert gpu.chs_batch_chords(None, 1, 0.5, o) == _lib.CHS_EINVAL
+    assert gpu.chs_batch_chords_hist(None, nb, h) == _lib.CHS_EINVAL
+    assert gpu.chs_batch_chords_hist(b._h, nb, h) == _lib.CHS_ESTATE                         # none of them was a look
+    assert gpu.chs_batch_chords(b._h, 1, 0.5, o) == _lib.CHS_OK
+    assert gpu.chs_batch_chords_hist(b._h, nb + 1, h) == _lib.CHS_EINVAL
+    assert f"expected {nb}" in gpu.chs_last_error().decode()
+    assert gpu.chs_batch_chords_hist(b._h, nb, None) == _lib.CHS_EINVAL
+    assert gpu.chs_batch_chords_hist(b._h, nb, h) == _lib.CHS_OK
+    co = chords.Chords(out, 128, 0.5, hist=hist[:8 * nb].reshape(2, 2, 2, nb))
+    assert co.n('below') == int((bs.solvers[1]._engine.get_U() < 0.5).sum())
+    bs.close(fetch_U=False)
