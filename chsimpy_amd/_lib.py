@@ -296,8 +296,78 @@ def test_math(which, a, b=None, device=0):
     return out
 
 
-class Engine:
+class _Looks:
+    """The looks at a thresholded field that go member by member, written once for `Engine` and `Batch`: the same calls
+    but for the prefix of the symbol (`_prefix`: ``chs_`` or ``chs_batch_``) and what stands in front of the threshold
+    (`lead`: nothing, or the member).  A batch has one set of buffers, so what is fetched is that of its last look."""
+
+    def _look_call(self, name, *args):
+        what = self._prefix + name
+        self._check(getattr(self.lib, what)(self._h, *args), what)
+
+    def _components(self, lead, threshold, connectivity, side):
+        out = np.empty(CHS_CC_WORDS, dtype=np.int64)
+        self._look_call('components', *lead, float(threshold), int(connectivity), int(side), _i64ptr(out))
+        self._cc_count = int(out[0])
+        return out
+
+    def components_table(self):
+        """int32 [count][6] of the last look: first, area, imin, imax, jmin, jmax."""
+        out = np.empty((self._cc_count, CHS_CC_COLS), dtype=np.int32)
+        self._look_call('components_table', self._cc_count, _i32ptr(out))
+        return out
+
+    def components_labels(self):
+        """int32 [N][N] of the last look: the component's number, -1 for background."""
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._look_call('components_labels', _i32ptr(out))
+        return out
+
+    def _components_look(self, lead, threshold, connectivity, side, table, labels):
+        words = self._components(lead, threshold, connectivity, side)
+        return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
+
+    def _distance(self, lead, threshold, side):
+        out = np.empty(CHS_DT_WORDS, dtype=np.int64)
+        self._look_call('distance', *lead, float(threshold), int(side), _i64ptr(out))
+        return out
+
+    def distance_hist(self):
+        """int64 [chs_distance_bins(N)] of the last look: the foreground pixels by radius bin."""
+        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
+        self._look_call('distance_hist', len(out), _i64ptr(out))
+        return out
+
+    def distance_map(self):
+        """int32 [N][N] of the last look: the squared distances."""
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._look_call('distance_map', _i32ptr(out))
+        return out
+
+    def _distance_look(self, lead, threshold, side, hist, map):
+        words = self._distance(lead, threshold, side)
+        return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
+
+    def _chords(self, lead, threshold):
+        out = np.empty(CHS_CH_WORDS, dtype=np.int64)
+        self._look_call('chords', *lead, float(threshold), _i64ptr(out))
+        return out
+
+    def chords_hist(self):
+        """int64 [2][2][2][chs_chords_bins(N)] of the last look: the chords by phase, direction, class and length."""
+        nb = int(self.lib.chs_chords_bins(self.N))
+        out = np.empty((2, 2, 2, nb), dtype=np.int64)
+        self._look_call('chords_hist', nb, _i64ptr(out))
+        return out
+
+    def _chords_look(self, lead, threshold, hist):
+        words = self._chords(lead, threshold)
+        return words, (self.chords_hist() if hist else None)
+
+
+class Engine(_Looks):
     """One device-resident simulation (an opaque ``chs_handle``)."""
+    _prefix = 'chs_'
 
     def __init__(self, consts: chs_consts, lam):
         self.lib = load()
@@ -420,97 +490,54 @@ class Engine:
         self._check(self.lib.chs_morphology(self._h, float(threshold), _i64ptr(out)), 'chs_morphology')
         return out
 
-    def morphology_ms(self):
-        """Device time (ms) of the last `morphology`."""
-        ms = C.c_double(0.0)
-        self._check(self.lib.chs_morphology_last_ms(self._h, C.byref(ms)), 'chs_morphology_last_ms')
-        return float(ms.value)
-
     def components(self, threshold, connectivity=4, side=CHS_CC_BELOW):
         """The seven int64 summary words of the connected components of the field the device holds (chs_components;
         chsimpy_amd/components.py names them).  Table and labels of this look: `components_table`, `components_labels`."""
-        out = np.empty(CHS_CC_WORDS, dtype=np.int64)
-        self._check(self.lib.chs_components(self._h, float(threshold), int(connectivity), int(side), _i64ptr(out)), 'chs_components')
-        self._cc_count = int(out[0])
-        return out
-
-    def components_table(self):
-        """int32 [count][6] of the last look: first, area, imin, imax, jmin, jmax."""
-        out = np.empty((self._cc_count, CHS_CC_COLS), dtype=np.int32)
-        self._check(self.lib.chs_components_table(self._h, self._cc_count, _i32ptr(out)), 'chs_components_table')
-        return out
-
-    def components_labels(self):
-        """int32 [N][N] of the last look: the component's number, -1 for background."""
-        out = np.empty((self.N, self.N), dtype=np.int32)
-        self._check(self.lib.chs_components_labels(self._h, _i32ptr(out)), 'chs_components_labels')
-        return out
+        return self._components((), threshold, connectivity, side)
 
     def components_look(self, threshold, connectivity, side, table=True, labels=False):
         """One look with what belongs to it: (words, table or None, labels or None)."""
-        words = self.components(threshold, connectivity, side)
-        return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
+        return self._components_look((), threshold, connectivity, side, table, labels)
 
     def distance(self, threshold, side=CHS_CC_BELOW):
         """The five int64 summary words of the distance transform of the field the device holds (chs_distance;
         chsimpy_amd/distance.py names them).  Histogram and map of this look: `distance_hist`, `distance_map`."""
-        out = np.empty(CHS_DT_WORDS, dtype=np.int64)
-        self._check(self.lib.chs_distance(self._h, float(threshold), int(side), _i64ptr(out)), 'chs_distance')
-        return out
-
-    def distance_hist(self):
-        """int64 [chs_distance_bins(N)] of the last look: the foreground pixels by radius bin."""
-        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
-        self._check(self.lib.chs_distance_hist(self._h, len(out), _i64ptr(out)), 'chs_distance_hist')
-        return out
-
-    def distance_map(self):
-        """int32 [N][N] of the last look: the squared distances."""
-        out = np.empty((self.N, self.N), dtype=np.int32)
-        self._check(self.lib.chs_distance_map(self._h, _i32ptr(out)), 'chs_distance_map')
-        return out
+        return self._distance((), threshold, side)
 
     def distance_look(self, threshold, side, hist=True, map=False):
         """One look with what belongs to it: (words, histogram or None, map or None)."""
-        words = self.distance(threshold, side)
-        return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
-
-    def distance_ms(self):
-        """Device time (ms) of the last `distance`."""
-        ms = C.c_double(0.0)
-        self._check(self.lib.chs_distance_last_ms(self._h, C.byref(ms)), 'chs_distance_last_ms')
-        return float(ms.value)
+        return self._distance_look((), threshold, side, hist, map)
 
     def chords(self, threshold):
         """The 24 int64 summary words of the chord lengths of the field the device holds (chs_chords;
         chsimpy_amd/chords.py names them).  The histograms of this look: `chords_hist`."""
-        out = np.empty(CHS_CH_WORDS, dtype=np.int64)
-        self._check(self.lib.chs_chords(self._h, float(threshold), _i64ptr(out)), 'chs_chords')
-        return out
-
-    def chords_hist(self):
-        """int64 [2][2][2][chs_chords_bins(N)] of the last look: the chords by phase, direction, class and length."""
-        nb = int(self.lib.chs_chords_bins(self.N))
-        out = np.empty((2, 2, 2, nb), dtype=np.int64)
-        self._check(self.lib.chs_chords_hist(self._h, nb, _i64ptr(out)), 'chs_chords_hist')
-        return out
+        return self._chords((), threshold)
 
     def chords_look(self, threshold, hist=True):
         """One look with what belongs to it: (words, histograms or None)."""
-        words = self.chords(threshold)
-        return words, (self.chords_hist() if hist else None)
+        return self._chords_look((), threshold, hist)
 
-    def chords_ms(self):
-        """Device time (ms) of the last `chords`."""
+    def _last_ms(self, symbol):
+        """Device time (ms) of the last look of a kind, by the symbol that answers it."""
         ms = C.c_double(0.0)
-        self._check(self.lib.chs_chords_last_ms(self._h, C.byref(ms)), 'chs_chords_last_ms')
+        self._check(getattr(self.lib, symbol)(self._h, C.byref(ms)), symbol)
         return float(ms.value)
+
+    def morphology_ms(self):
+        """Device time (ms) of the last `morphology`."""
+        return self._last_ms('chs_morphology_last_ms')
 
     def components_ms(self):
         """Device time (ms) of the last `components`."""
-        ms = C.c_double(0.0)
-        self._check(self.lib.chs_components_last_ms(self._h, C.byref(ms)), 'chs_components_last_ms')
-        return float(ms.value)
+        return self._last_ms('chs_components_last_ms')
+
+    def distance_ms(self):
+        """Device time (ms) of the last `distance`."""
+        return self._last_ms('chs_distance_last_ms')
+
+    def chords_ms(self):
+        """Device time (ms) of the last `chords`."""
+        return self._last_ms('chs_chords_last_ms')
 
     @property
     def engine(self):
@@ -539,9 +566,10 @@ def _u128_pair(x):
     return (C.c_uint64 * 2)((int(x) >> 64) & m64, int(x) & m64)
 
 
-class Batch:
+class Batch(_Looks):
     """B device-resident simulations of one N, dtype and device advanced together (an opaque ``chs_batch``):
     every step kernel is launched once for all members.  Member-wise the methods are those of `Engine`."""
+    _prefix = 'chs_batch_'
 
     def __init__(self, consts_list, lam):
         self.lib = load()
@@ -647,66 +675,25 @@ class Batch:
         return out
 
     def components(self, member, threshold, connectivity=4, side=CHS_CC_BELOW):
-        """`Engine.components` of one member (chs_batch_components): the batch has one set of buffers, so the table and
-        the labels are those of its last look."""
-        out = np.empty(CHS_CC_WORDS, dtype=np.int64)
-        self._check(self.lib.chs_batch_components(self._h, int(member), float(threshold), int(connectivity), int(side),
-                                                  _i64ptr(out)), 'chs_batch_components')
-        self._cc_count = int(out[0])
-        return out
-
-    def components_table(self):
-        out = np.empty((self._cc_count, CHS_CC_COLS), dtype=np.int32)
-        self._check(self.lib.chs_batch_components_table(self._h, self._cc_count, _i32ptr(out)), 'chs_batch_components_table')
-        return out
-
-    def components_labels(self):
-        out = np.empty((self.N, self.N), dtype=np.int32)
-        self._check(self.lib.chs_batch_components_labels(self._h, _i32ptr(out)), 'chs_batch_components_labels')
-        return out
+        """`Engine.components` of one member (chs_batch_components)."""
+        return self._components((int(member),), threshold, connectivity, side)
 
     def components_look(self, member, threshold, connectivity, side, table=True, labels=False):
-        words = self.components(member, threshold, connectivity, side)
-        return words, (self.components_table() if table else None), (self.components_labels() if labels else None)
+        return self._components_look((int(member),), threshold, connectivity, side, table, labels)
 
     def distance(self, member, threshold, side=CHS_CC_BELOW):
-        """`Engine.distance` of one member (chs_batch_distance): the batch has one set of buffers, so the histogram and
-        the map are those of its last look."""
-        out = np.empty(CHS_DT_WORDS, dtype=np.int64)
-        self._check(self.lib.chs_batch_distance(self._h, int(member), float(threshold), int(side), _i64ptr(out)),
-                    'chs_batch_distance')
-        return out
-
-    def distance_hist(self):
-        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
-        self._check(self.lib.chs_batch_distance_hist(self._h, len(out), _i64ptr(out)), 'chs_batch_distance_hist')
-        return out
-
-    def distance_map(self):
-        out = np.empty((self.N, self.N), dtype=np.int32)
-        self._check(self.lib.chs_batch_distance_map(self._h, _i32ptr(out)), 'chs_batch_distance_map')
-        return out
+        """`Engine.distance` of one member (chs_batch_distance)."""
+        return self._distance((int(member),), threshold, side)
 
     def distance_look(self, member, threshold, side, hist=True, map=False):
-        words = self.distance(member, threshold, side)
-        return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
+        return self._distance_look((int(member),), threshold, side, hist, map)
 
     def chords(self, member, threshold):
-        """`Engine.chords` of one member (chs_batch_chords): the batch has one set of buffers, so the histograms are
-        those of its last look."""
-        out = np.empty(CHS_CH_WORDS, dtype=np.int64)
-        self._check(self.lib.chs_batch_chords(self._h, int(member), float(threshold), _i64ptr(out)), 'chs_batch_chords')
-        return out
-
-    def chords_hist(self):
-        nb = int(self.lib.chs_chords_bins(self.N))
-        out = np.empty((2, 2, 2, nb), dtype=np.int64)
-        self._check(self.lib.chs_batch_chords_hist(self._h, nb, _i64ptr(out)), 'chs_batch_chords_hist')
-        return out
+        """`Engine.chords` of one member (chs_batch_chords)."""
+        return self._chords((int(member),), threshold)
 
     def chords_look(self, member, threshold, hist=True):
-        words = self.chords(member, threshold)
-        return words, (self.chords_hist() if hist else None)
+        return self._chords_look((int(member),), threshold, hist)
 
     def get_state(self, member):
         s = chs_state()

@@ -30,6 +30,8 @@ member stops or has done its call the next one in member order takes its seat on
 towards the end of every call; a queue of all the runs keeps S of them going.  The results are bit for bit the plain
 batch's.
 """
+import functools
+
 import numpy as np
 
 from . import _lib
@@ -124,23 +126,13 @@ class _Member:
     def morphology(self, threshold):
         return self._b.morphology(threshold, self._m)
 
-    def components(self, threshold, connectivity=4, side=0):
-        return self._b.components(self._m, threshold, connectivity, side)
+    _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look')
 
-    def components_look(self, threshold, connectivity, side, table=True, labels=False):
-        return self._b.components_look(self._m, threshold, connectivity, side, table, labels)
-
-    def distance(self, threshold, side=0):
-        return self._b.distance(self._m, threshold, side)
-
-    def distance_look(self, threshold, side, hist=True, map=False):
-        return self._b.distance_look(self._m, threshold, side, hist, map)
-
-    def chords(self, threshold):
-        return self._b.chords(self._m, threshold)
-
-    def chords_look(self, threshold, hist=True):
-        return self._b.chords_look(self._m, threshold, hist)
+    def __getattr__(self, name):
+        """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
+        if name in self._LOOKS:
+            return functools.partial(getattr(self._b, name), self._m)
+        raise AttributeError(name)
 
     def close(self):
         pass  # (the batch owns the device state)
@@ -276,14 +268,7 @@ class BatchSolver:
         b = self._get_batch()
         for s in self.solvers:
             s._push_edited_U()
-        if threshold is None:
-            ts = [float(s.params.threshold) for s in self.solvers]
-        elif np.ndim(threshold) == 0:
-            ts = [float(threshold)] * len(self.solvers)
-        else:
-            ts = [float(t) for t in threshold]
-            if len(ts) != len(self.solvers):
-                raise ValueError(f"{len(self.solvers)} thresholds are needed, got {len(ts)}")
+        ts = [float(s.params.threshold) if t is None else t for s, t in zip(self.solvers, self._member_thresholds(threshold))]
         if member is not None:
             s = self.solvers[member]
             return morphology.Morphology(b.morphology(ts[member], member), s.params.N, ts[member], s.solution.delx)
@@ -302,38 +287,27 @@ class BatchSolver:
             raise ValueError(f"{len(self.solvers)} thresholds are needed, got {len(ts)}")
         return ts
 
-    def components(self, member=None, threshold=None, connectivity=4, side='below', table=True, labels=False):
-        """The members' connected components (`Solver.components`): a list of one `components.Components` per member,
-        looked at member by member on the batch's stream with the batch's one set of buffers, or the one of ``member``.
-        ``threshold``: one value for all, one per member, or None for every member's own ``params.threshold``.  The
-        members' runs do not notice the looks."""
+    def _member_by_member(self, look, member, threshold, *args):
+        """`Solver.<look>(threshold, *args)` of every member, one after the other on the batch's stream with the batch's
+        one set of buffers, as a list -- or that of ``member`` alone.  ``threshold``: one value for all, one per member,
+        or None for every member's own ``params.threshold``.  The members' runs do not notice the looks."""
         self._get_batch()
         ts = self._member_thresholds(threshold)
         if member is not None:
-            return self.solvers[member].components(ts[member], connectivity, side, table, labels)
-        return [s.components(t, connectivity, side, table, labels) for s, t in zip(self.solvers, ts)]
+            return getattr(self.solvers[member], look)(ts[member], *args)
+        return [getattr(s, look)(t, *args) for s, t in zip(self.solvers, ts)]
+
+    def components(self, member=None, threshold=None, connectivity=4, side='below', table=True, labels=False):
+        """The members' connected components (`Solver.components`), a `components.Components` each: _member_by_member."""
+        return self._member_by_member('components', member, threshold, connectivity, side, table, labels)
 
     def distance(self, member=None, threshold=None, side='below', hist=True, map=False):
-        """The members' distance transforms (`Solver.distance`): a list of one `distance.Distance` per member, looked at
-        member by member on the batch's stream with the batch's one set of buffers, or the one of ``member``.
-        ``threshold``: one value for all, one per member, or None for every member's own ``params.threshold``.  The
-        members' runs do not notice the looks."""
-        self._get_batch()
-        ts = self._member_thresholds(threshold)
-        if member is not None:
-            return self.solvers[member].distance(ts[member], side, hist, map)
-        return [s.distance(t, side, hist, map) for s, t in zip(self.solvers, ts)]
+        """The members' distance transforms (`Solver.distance`), a `distance.Distance` each: _member_by_member."""
+        return self._member_by_member('distance', member, threshold, side, hist, map)
 
     def chords(self, member=None, threshold=None, hist=True):
-        """The members' chord lengths (`Solver.chords`): a list of one `chords.Chords` per member, looked at member by
-        member on the batch's stream with the batch's one set of buffers, or the one of ``member``.  ``threshold``: one
-        value for all, one per member, or None for every member's own ``params.threshold``.  The members' runs do not
-        notice the looks."""
-        self._get_batch()
-        ts = self._member_thresholds(threshold)
-        if member is not None:
-            return self.solvers[member].chords(ts[member], hist)
-        return [s.chords(t, hist) for s, t in zip(self.solvers, ts)]
+        """The members' chord lengths (`Solver.chords`), a `chords.Chords` each: _member_by_member."""
+        return self._member_by_member('chords', member, threshold, hist)
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

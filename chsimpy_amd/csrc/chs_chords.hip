@@ -31,11 +31,9 @@
 //   3  k_ch_fin    one workgroup reduces the eight histograms to the 24 words by a fixed tree and checks the look: per
 //                  direction the chords add up to N^2 pixels, and the cut chords of both phases are N to 2 N.
 // Nothing of the handle is written and nothing the step loop owns is read: its field alone.
-#include <cmath>
 #include <cstring>
-#include <new>
 
-#include "chs_common.h"
+#include "chs_look.h"
 #include "chs_cc_host.h"   // chs_cc::fg_of: phase 0 is the foreground of chs_components with CHS_CC_BELOW
 
 #define CHS_CH_WORD 64                      // pixels of a line in one word; rows of a band of k_ch_mask
@@ -64,25 +62,22 @@ typedef long long ch_i64;
 typedef unsigned long long ch_u64;
 static_assert(sizeof(ch_i64) == sizeof(int64_t), "the result words are int64");
 
-// (the field is device memory: loads through global, not flat, instructions -- chs_morphology.hip, MORPH_GLOBAL)
-#define CH_GLOBAL __attribute__((address_space(1)))
-
 // ---- phase 1 ---------------------------------------------------------------------------------------------------------
 // grid (column strips, bands).  Thread tid owns column blockIdx.x CH_THREADS + tid and the band's 64 rows of it; its
 // wavefront owns the 64 columns of word j / 64 of the rows.
 template <typename T, bool NT>
 __global__ __launch_bounds__(CH_THREADS) void k_ch_mask(const void* Uv, int N, int nb, double t, ch_u64* __restrict__ cols,
                                                         ch_u64* __restrict__ rows) {
-  const T CH_GLOBAL* U = (const T CH_GLOBAL*)Uv;
+  const T CHS_GLOBAL* U = (const T CHS_GLOBAL*)Uv;
   const int j = blockIdx.x * CH_THREADS + threadIdx.x, i0 = blockIdx.y * CHS_CH_WORD;
   const int lane = threadIdx.x % CHS_WAVE, w = j / CHS_CH_WORD;   // (w is the same for the whole wavefront)
   const bool inside = j < N;
-  const T CH_GLOBAL* col = U + (inside ? j : N - 1);
+  const T CHS_GLOBAL* col = U + (inside ? j : N - 1);
   ch_u64 cw = 0, rw = 0;
 #pragma unroll 8
   for (int r = 0; r < CHS_CH_WORD; ++r) {
     const int i = i0 + r;
-    const T CH_GLOBAL* src = col + (size_t)(i < N ? i : N - 1) * N;
+    const T CHS_GLOBAL* src = col + (size_t)(i < N ? i : N - 1) * N;
     const T x = NT ? __builtin_nontemporal_load(src) : *src;
     const bool p0 = inside && i < N && chs_cc::fg_of((double)x, t, 0);
     cw |= (ch_u64)(p0 ? 1 : 0) << r;
@@ -250,35 +245,25 @@ struct ChResult {   // pinned
   ch_i64 out[CHS_CH_WORDS];
 };
 
-struct ChBuf {
-  int N = 0, nb = 0, nbins = 0;
+struct ChBuf : LookBase {   // have: hist is the look's snapshot
+  int nb = 0, nbins = 0;
   ch_u64* planes = nullptr;     // [2][nb][N]: the column plane (the words of the columns), then the row plane
   ch_u64* hist = nullptr;       // [2][2][2][nbins]
   ch_i64* out = nullptr;        // [CHS_CH_WORDS]
   int* words = nullptr;         // [CH_NW]
   ChResult* hRes = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double ms = -1.0;
-  bool have = false;            // a look has succeeded: hist is its snapshot
 };
 
 void ch_release(ChBuf* s) {
   if (!s) return;
   hipFree(s->planes); hipFree(s->hist); hipFree(s->out); hipFree(s->words);
   if (s->hRes) hipHostFree(s->hRes);
-  for (auto e : s->ev) if (e) hipEventDestroy(e);
+  look_release_events(s);
   delete s;
 }
 
-int ch_buffers(void** buf, int N) {
-  ChBuf* s = (ChBuf*)*buf;
-  if (s && s->N == N) return CHS_OK;
-  ch_release(s);
-  *buf = nullptr;
-  s = new (std::nothrow) ChBuf();
-  if (!s) { chs_set_error("out of host memory"); return CHS_EINVAL; }
-  *buf = s;   // (freed with its owner whatever fails below)
-  s->N = N;
+int ch_alloc(ChBuf* s) {
+  const int N = s->N;
   s->nb = (N + CHS_CH_WORD - 1) / CHS_CH_WORD;
   s->nbins = chs_chords_bins(N);
   CHS_HIP(hipMalloc(&s->planes, sizeof(ch_u64) * 2 * (size_t)s->nb * N));
@@ -286,7 +271,6 @@ int ch_buffers(void** buf, int N) {
   CHS_HIP(hipMalloc(&s->out, sizeof(ch_i64) * CHS_CH_WORDS));
   CHS_HIP(hipMalloc(&s->words, sizeof(int) * CH_NW));
   CHS_HIP(hipHostMalloc((void**)&s->hRes, sizeof(ChResult), hipHostMallocDefault));
-  for (auto& e : s->ev) CHS_HIP(hipEventCreate(&e));
   return CHS_OK;
 }
 
@@ -305,7 +289,7 @@ int launch_mask(const ChBuf* s, const void* U, double t, hipStream_t st) {
 
 int ch_run(ChBuf* s, Engine* E, hipStream_t st, double t, const std::string& who) {
   const int N = s->N;
-  s->have = false; s->ms = -1.0;
+  look_forget(s);
   CHS_HIP(hipMemsetAsync(s->words, 0, sizeof(int) * CH_NW, st));
   CHS_HIP(hipMemsetAsync(s->hist, 0, sizeof(ch_u64) * CH_HISTS * (size_t)s->nbins, st));
   CHS_HIP(hipEventRecord(s->ev[0], st));
@@ -328,11 +312,7 @@ int ch_run(ChBuf* s, Engine* E, hipStream_t st, double t, const std::string& who
     chs_set_error(who + ": self-check failed:" + m);
     return CHS_ECHECK;
   }
-  float ms = 0.f;
-  CHS_HIP(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-  s->ms = ms;
-  s->have = true;
-  return CHS_OK;
+  return look_end(s);
 }
 }  // namespace
 
@@ -343,20 +323,15 @@ void chs_ch_free(void** buf) {
 }
 
 void chs_ch_forget(void* buf) {
-  if (!buf) return;
-  ChBuf* s = (ChBuf*)buf;
-  s->have = false; s->ms = -1.0;
+  if (buf) look_forget((ChBuf*)buf);
 }
 
 int chs_ch_look(Engine* E, hipStream_t st, void** buf, double threshold, int64_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
-  if (!std::isfinite(threshold)) { chs_set_error(who + ": the threshold must be finite"); return CHS_EINVAL; }
-  if (E->N > CH_MAX_N) { chs_set_error(who + ": N above " + std::to_string(CH_MAX_N)); return CHS_EINVAL; }
-  if (!E->have_U) { chs_set_error(who + ": no field (chs_set_U / chs_init_U_pcg64 first)"); return CHS_ESTATE; }
-  CHS_HIP(hipSetDevice(E->hc.device));
   int rc;
-  if ((rc = ch_buffers(buf, E->N))) return rc;
+  if ((rc = look_check_args(out, threshold, who))) return rc;
+  if ((rc = look_check_field(E, CH_MAX_N, who))) return rc;
+  if ((rc = look_buffers<ChBuf>(buf, E->N, ch_alloc, ch_release))) return rc;
   ChBuf* s = (ChBuf*)*buf;
   if ((rc = ch_run(s, E, st, threshold, who))) return rc;
   memcpy(out, s->hRes->out, sizeof(int64_t) * CHS_CH_WORDS);
@@ -365,14 +340,11 @@ int chs_ch_look(Engine* E, hipStream_t st, void** buf, double threshold, int64_t
 
 int chs_ch_hist(void* buf, int device, hipStream_t st, int32_t nbins, int64_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
   const ChBuf* s = (const ChBuf*)buf;
-  if (!s || !s->have) { chs_set_error(who + ": no look so far"); return CHS_ESTATE; }
+  int rc;
+  if ((rc = look_ready(s, out, who))) return rc;
   if (nbins != s->nbins) { chs_set_error(who + ": nbins = " + std::to_string(nbins) + ", expected " + std::to_string(s->nbins)); return CHS_EINVAL; }
-  CHS_HIP(hipSetDevice(device));
-  CHS_HIP(hipMemcpyAsync(out, s->hist, sizeof(int64_t) * CH_HISTS * (size_t)nbins, hipMemcpyDeviceToHost, st));
-  CHS_HIP(hipStreamSynchronize(st));
-  return CHS_OK;
+  return look_fetch(device, st, out, s->hist, sizeof(int64_t) * CH_HISTS * (size_t)nbins);
 }
 
 extern "C" int32_t chs_chords_bins(int32_t N) { return N < 1 ? 0 : N + 1; }
@@ -390,12 +362,7 @@ extern "C" int chs_chords_hist(chs_handle h, int32_t nbins, int64_t* out) {
 }
 
 extern "C" int chs_chords_last_ms(chs_handle h, double* ms) {
-  Engine* E = (Engine*)h;
-  if (!E || !ms) { chs_set_error("chs_chords_last_ms: null argument"); return CHS_EINVAL; }
-  const ChBuf* s = (const ChBuf*)E->ch;
-  if (!s || s->ms < 0.0) { chs_set_error("chs_chords_last_ms: no chs_chords call so far"); return CHS_ESTATE; }
-  *ms = s->ms;
-  return CHS_OK;
+  return look_last_ms(h, h ? (const ChBuf*)((Engine*)h)->ch : nullptr, ms, "chs_chords");
 }
 
 extern "C" int chs_chords_tile(int32_t* word_bits, int32_t* lines_per_group, int32_t* local_bins) {

@@ -29,9 +29,8 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <new>
 
-#include "chs_common.h"
+#include "chs_look.h"
 #include "chs_cc_host.h"
 
 #define CC_THREADS 256
@@ -52,17 +51,8 @@ static_assert(CHS_CC_TILE % CC_THREADS == 0 && CHS_CC_NUM_BLOCK % CC_THREADS == 
 static_assert(CHS_CC_TC % 4 == 0, "a 16-byte load stays inside a tile row");
 static_assert(CC_ITERS * CC_WAVES == CHS_WAVE, "k_cc_scatter scans its (iteration, wavefront) counts in one wavefront");
 
-typedef double cc_d2 __attribute__((ext_vector_type(2)));
-typedef float cc_f4 __attribute__((ext_vector_type(4)));
 typedef long long cc_i64;
 static_assert(sizeof(cc_i64) == sizeof(int64_t) && sizeof(chs_cc::Summary) == CHS_CC_WORDS * sizeof(int64_t), "the summary is the seven int64 words");
-
-// (the field is device memory: loads through global, not flat, instructions -- chs_morphology.hip, MORPH_GLOBAL)
-#define CC_GLOBAL __attribute__((address_space(1)))
-
-template <typename T> struct CcVec;
-template <> struct CcVec<double> { typedef cc_d2 type; static constexpr int V = 2; };
-template <> struct CcVec<float> { typedef cc_f4 type; static constexpr int V = 4; };
 
 // how find / unite read and min-update a label word (chs_cc_host.h): the tile's words in LDS ...
 struct CcLdsWords {
@@ -86,8 +76,7 @@ template <typename T, int V, bool NT>
 __global__ __launch_bounds__(CC_THREADS) void k_cc_tile(const void* Uv, int N, double t, int conn, int above,
                                                         int* __restrict__ L, int* __restrict__ words) {
   __shared__ int par[CHS_CC_TILE];
-  typedef const typename CcVec<T>::type CC_GLOBAL* VP;
-  const T CC_GLOBAL* U = (const T CC_GLOBAL*)Uv;
+  const T CHS_GLOBAL* U = (const T CHS_GLOBAL*)Uv;
   const int tid = threadIdx.x, i0 = blockIdx.y * CHS_CC_TR, j0 = blockIdx.x * CHS_CC_TC;
   unsigned fg = 0, in = 0;   // bit it V + e: the pixel is foreground / inside the grid
 #pragma unroll
@@ -95,15 +84,9 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_tile(const void* Uv, int N, d
     const int k = (it * CC_THREADS + tid) * V;
     const int i = i0 + k / CHS_CC_TC, j = j0 + k % CHS_CC_TC;
     const bool inside = i < N && j < N;   // (V > 1: N and j are multiples of V, so j < N is j + V - 1 < N)
-    const T CC_GLOBAL* src = U + (size_t)(i < N ? i : N - 1) * N + (j < N ? j : N - V);
+    const T CHS_GLOBAL* src = U + (size_t)(i < N ? i : N - 1) * N + (j < N ? j : N - V);
     T x[V];
-    if constexpr (V == 1) {
-      x[0] = NT ? __builtin_nontemporal_load(src) : *src;
-    } else {
-      const typename CcVec<T>::type v = NT ? __builtin_nontemporal_load(reinterpret_cast<VP>(src)) : *reinterpret_cast<VP>(src);
-#pragma unroll
-      for (int e = 0; e < V; ++e) x[e] = v[e];
-    }
+    chs_load<T, V, NT>(src, x);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       const bool f = inside && chs_cc::fg_of((double)x[e], t, above);
@@ -396,8 +379,8 @@ struct CcResult {   // pinned
   chs_cc::Summary out;
 };
 
-struct CcBuf {
-  int N = 0, nblk = 0;
+struct CcBuf : LookBase {   // have: L, id, table and count are the look's snapshot
+  int nblk = 0;
   int* L = nullptr;             // [N * N] labels: the root's index, -1 for background
   int* id = nullptr;            // [N * N] the number at every root; the label image after k_cc_labels
   int* blk = nullptr;           // [nblk] the numbering's block counts, then offsets
@@ -407,9 +390,6 @@ struct CcBuf {
   chs_cc::Summary* part = nullptr;   // [CC_SUM_BLOCKS]
   chs_cc::Summary* out = nullptr;    // [1]
   CcResult* hRes = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double ms = -1.0;
-  bool have = false;            // a look has succeeded: L, id, table and count are its snapshot
   bool labelled = false;        // k_cc_labels has run behind it
   cc_i64 count = 0;
 };
@@ -418,19 +398,12 @@ void cc_release(CcBuf* s) {
   if (!s) return;
   hipFree(s->L); hipFree(s->id); hipFree(s->blk); hipFree(s->table); hipFree(s->words); hipFree(s->part); hipFree(s->out);
   if (s->hRes) hipHostFree(s->hRes);
-  for (auto e : s->ev) if (e) hipEventDestroy(e);
+  look_release_events(s);
   delete s;
 }
 
-int cc_buffers(void** buf, int N) {
-  CcBuf* s = (CcBuf*)*buf;
-  if (s && s->N == N) return CHS_OK;
-  cc_release(s);
-  *buf = nullptr;
-  s = new (std::nothrow) CcBuf();
-  if (!s) { chs_set_error("out of host memory"); return CHS_EINVAL; }
-  *buf = s;   // (freed with its owner whatever fails below)
-  s->N = N;
+int cc_alloc(CcBuf* s) {
+  const int N = s->N;
   s->nblk = chs_cc::num_blocks(N);
   const size_t n2 = (size_t)N * N;
   CHS_HIP(hipMalloc(&s->L, sizeof(int) * n2));
@@ -440,13 +413,12 @@ int cc_buffers(void** buf, int N) {
   CHS_HIP(hipMalloc(&s->part, sizeof(chs_cc::Summary) * CC_SUM_BLOCKS));
   CHS_HIP(hipMalloc(&s->out, sizeof(chs_cc::Summary)));
   CHS_HIP(hipHostMalloc((void**)&s->hRes, sizeof(CcResult), hipHostMallocDefault));
-  for (auto& e : s->ev) CHS_HIP(hipEventCreate(&e));
   return CHS_OK;
 }
 
 template <typename T>
 int launch_tile(const CcBuf* s, const void* U, double t, int conn, int side, hipStream_t st) {
-  constexpr int V = CcVec<T>::V;
+  constexpr int V = ChsVec<T>::V;
   const int N = s->N;
   const dim3 grid(chs_cc::tiles_of(N, CHS_CC_TC), chs_cc::tiles_of(N, CHS_CC_TR));
   // a read-once sweep: where the step loop's arrays fill the Infinity Cache it must not displace them
@@ -480,7 +452,8 @@ int cc_run(CcBuf* s, Engine* E, hipStream_t st, double t, int conn, int side, co
   const int N = s->N, n2 = N * N;
   const int tx = chs_cc::tiles_of(N, CHS_CC_TC), ntiles = tx * chs_cc::tiles_of(N, CHS_CC_TR);
   const int pixBlocks = (n2 + CC_THREADS - 1) / CC_THREADS;
-  s->have = false; s->labelled = false; s->ms = -1.0;
+  look_forget(s);
+  s->labelled = false;
   CHS_HIP(hipMemsetAsync(s->words, 0, sizeof(int) * CC_NW, st));
   CHS_HIP(hipEventRecord(s->ev[0], st));
   int rc = E->dtype == CHS_F64 ? launch_tile<double>(s, E->dU, t, conn, side, st) : launch_tile<float>(s, E->dU, t, conn, side, st);
@@ -525,12 +498,8 @@ int cc_run(CcBuf* s, Engine* E, hipStream_t st, double t, int conn, int side, co
     chs_set_error(who + ": self-check failed:" + cc_failure(s->hRes->words));
     return CHS_ECHECK;
   }
-  float ms = 0.f;
-  CHS_HIP(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-  s->ms = ms;
   s->count = C;
-  s->have = true;
-  return CHS_OK;
+  return look_end(s);
 }
 }  // namespace
 
@@ -543,21 +512,19 @@ void chs_cc_free(void** buf) {
 void chs_cc_forget(void* buf) {
   if (!buf) return;
   CcBuf* s = (CcBuf*)buf;
-  s->have = false; s->labelled = false; s->ms = -1.0; s->count = 0;
+  look_forget(s);
+  s->labelled = false; s->count = 0;
 }
 
 int chs_cc_look(Engine* E, hipStream_t st, void** buf, double threshold, int32_t connectivity, int32_t side, int64_t* out,
                 const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
-  if (!std::isfinite(threshold)) { chs_set_error(who + ": the threshold must be finite"); return CHS_EINVAL; }
+  int rc;
+  if ((rc = look_check_args(out, threshold, who))) return rc;
   if (connectivity != 4 && connectivity != 8) { chs_set_error(who + ": the connectivity is 4 or 8"); return CHS_EINVAL; }
   if (side != CHS_CC_BELOW && side != CHS_CC_ABOVE) { chs_set_error(who + ": the side is CHS_CC_BELOW (0) or CHS_CC_ABOVE (1)"); return CHS_EINVAL; }
-  if (E->N > CHS_CC_MAX_N) { chs_set_error(who + ": N above " + std::to_string(CHS_CC_MAX_N)); return CHS_EINVAL; }
-  if (!E->have_U) { chs_set_error(who + ": no field (chs_set_U / chs_init_U_pcg64 first)"); return CHS_ESTATE; }
-  CHS_HIP(hipSetDevice(E->hc.device));
-  int rc;
-  if ((rc = cc_buffers(buf, E->N))) return rc;
+  if ((rc = look_check_field(E, CHS_CC_MAX_N, who))) return rc;
+  if ((rc = look_buffers<CcBuf>(buf, E->N, cc_alloc, cc_release))) return rc;
   CcBuf* s = (CcBuf*)*buf;
   if ((rc = cc_run(s, E, st, threshold, connectivity, side, who))) return rc;
   memcpy(out, &s->hRes->out, sizeof(int64_t) * CHS_CC_WORDS);
@@ -566,22 +533,19 @@ int chs_cc_look(Engine* E, hipStream_t st, void** buf, double threshold, int32_t
 
 int chs_cc_table(void* buf, int device, hipStream_t st, int64_t rows, int32_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
   const CcBuf* s = (const CcBuf*)buf;
-  if (!s || !s->have) { chs_set_error(who + ": no look so far"); return CHS_ESTATE; }
+  int rc;
+  if ((rc = look_ready(s, out, who))) return rc;
   if (rows != s->count) { chs_set_error(who + ": rows = " + std::to_string(rows) + ", the last look counted " + std::to_string(s->count)); return CHS_EINVAL; }
   if (rows == 0) return CHS_OK;
-  CHS_HIP(hipSetDevice(device));
-  CHS_HIP(hipMemcpyAsync(out, s->table, sizeof(int32_t) * CHS_CC_COLS * (size_t)rows, hipMemcpyDeviceToHost, st));
-  CHS_HIP(hipStreamSynchronize(st));
-  return CHS_OK;
+  return look_fetch(device, st, out, s->table, sizeof(int32_t) * CHS_CC_COLS * (size_t)rows);
 }
 
 int chs_cc_labels(void* buf, int device, hipStream_t st, int32_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
   CcBuf* s = (CcBuf*)buf;
-  if (!s || !s->have) { chs_set_error(who + ": no look so far"); return CHS_ESTATE; }
+  int rc;
+  if ((rc = look_ready(s, out, who))) return rc;
   CHS_HIP(hipSetDevice(device));
   const int n2 = s->N * s->N;
   if (!s->labelled) {
@@ -613,12 +577,7 @@ extern "C" int chs_components_labels(chs_handle h, int32_t* out) {
 }
 
 extern "C" int chs_components_last_ms(chs_handle h, double* ms) {
-  Engine* E = (Engine*)h;
-  if (!E || !ms) { chs_set_error("chs_components_last_ms: null argument"); return CHS_EINVAL; }
-  const CcBuf* s = (const CcBuf*)E->cc;
-  if (!s || s->ms < 0.0) { chs_set_error("chs_components_last_ms: no chs_components call so far"); return CHS_ESTATE; }
-  *ms = s->ms;
-  return CHS_OK;
+  return look_last_ms(h, h ? (const CcBuf*)((Engine*)h)->cc : nullptr, ms, "chs_components");
 }
 
 extern "C" int chs_components_tile(int32_t* rows, int32_t* cols) {

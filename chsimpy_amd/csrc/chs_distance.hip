@@ -28,9 +28,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 
-#include "chs_common.h"
+#include "chs_look.h"
 #include "chs_cc_host.h"   // chs_cc::fg_of: the foreground is that of chs_components
 
 #define CHS_DT_BAND 64                      // rows of a band: the bits of one word
@@ -50,18 +49,9 @@ static_assert(CHS_DT_BAND == 64, "a band of a column is one 64-bit word");
 static_assert(2ll * (DT_MAX_N - 1) * (DT_MAX_N - 1) < CHS_DT_INF, "every finite D2 is below CHS_DT_INF");
 static_assert((long long)DT_DN_NONE < (1ll << 31) && (long long)DT_MAX_N + CHS_DT_INF < (1ll << 31), "the carries stay inside int32");
 
-typedef double dt_d2 __attribute__((ext_vector_type(2)));
-typedef float dt_f4 __attribute__((ext_vector_type(4)));
 typedef long long dt_i64;
 typedef unsigned long long dt_u64;
 static_assert(sizeof(dt_i64) == sizeof(int64_t), "the result words are int64");
-
-// (the field is device memory: loads through global, not flat, instructions -- chs_morphology.hip, MORPH_GLOBAL)
-#define DT_GLOBAL __attribute__((address_space(1)))
-
-template <typename T> struct DtVec;
-template <> struct DtVec<double> { typedef dt_d2 type; static constexpr int V = 2; };
-template <> struct DtVec<float> { typedef dt_f4 type; static constexpr int V = 4; };
 
 struct DtSummary {
   dt_i64 fg, d2max, first, sumd2, ninf;
@@ -93,23 +83,24 @@ __host__ __device__ inline int dt_isqrt(int v) {
 // clamped to one inside and masked: its bit stays 0, as if it were foreground, so it is nobody's nearest background.
 template <typename T, int V, bool NT>
 __global__ __launch_bounds__(DT_THREADS) void k_dt_mask(const void* Uv, int N, double t, int above, dt_u64* __restrict__ mask) {
-  typedef const typename DtVec<T>::type DT_GLOBAL* VP;
-  const T DT_GLOBAL* U = (const T DT_GLOBAL*)Uv;
+  typedef const typename ChsVec<T>::type CHS_GLOBAL* VP;
+  const T CHS_GLOBAL* U = (const T CHS_GLOBAL*)Uv;
   const int j = (blockIdx.x * DT_THREADS + threadIdx.x) * V, i0 = blockIdx.y * CHS_DT_BAND;
   const bool inside = j < N;   // (V > 1: N and j are multiples of V, so j < N is j + V - 1 < N)
-  const T DT_GLOBAL* col = U + (inside ? j : N - V);
+  const T CHS_GLOBAL* col = U + (inside ? j : N - V);
   dt_u64 m[V];
 #pragma unroll
   for (int e = 0; e < V; ++e) m[e] = 0;
 #pragma unroll 8
   for (int r = 0; r < CHS_DT_BAND; ++r) {
     const int i = i0 + r;
-    const T DT_GLOBAL* src = col + (size_t)(i < N ? i : N - 1) * N;
+    const T CHS_GLOBAL* src = col + (size_t)(i < N ? i : N - 1) * N;
     T x[V];
+    // (chs_load of chs_look.h, written out: behind the call the compiler schedules this unrolled loop otherwise)
     if constexpr (V == 1) {
       x[0] = NT ? __builtin_nontemporal_load(src) : *src;
     } else {
-      const typename DtVec<T>::type v = NT ? __builtin_nontemporal_load(reinterpret_cast<VP>(src)) : *reinterpret_cast<VP>(src);
+      const typename ChsVec<T>::type v = NT ? __builtin_nontemporal_load(reinterpret_cast<VP>(src)) : *reinterpret_cast<VP>(src);
 #pragma unroll
       for (int e = 0; e < V; ++e) x[e] = v[e];
     }
@@ -278,8 +269,8 @@ struct DtResult {   // pinned
   DtSummary out;
 };
 
-struct DtBuf {
-  int N = 0, nb = 0, nbins = 0;
+struct DtBuf : LookBase {   // have: D2 and hist are the look's snapshot
+  int nb = 0, nbins = 0;
   int* D2 = nullptr;            // [N * N]
   dt_u64* mask = nullptr;       // [nb][N] the background bits of every band of every column
   int* up = nullptr;            // [nb][N] the carries
@@ -289,28 +280,18 @@ struct DtBuf {
   DtSummary* out = nullptr;     // [1]
   int* words = nullptr;         // [DT_NW]
   DtResult* hRes = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double ms = -1.0;
-  bool have = false;            // a look has succeeded: D2 and hist are its snapshot
 };
 
 void dt_release(DtBuf* s) {
   if (!s) return;
   hipFree(s->D2); hipFree(s->mask); hipFree(s->up); hipFree(s->dn); hipFree(s->hist); hipFree(s->part); hipFree(s->out); hipFree(s->words);
   if (s->hRes) hipHostFree(s->hRes);
-  for (auto e : s->ev) if (e) hipEventDestroy(e);
+  look_release_events(s);
   delete s;
 }
 
-int dt_buffers(void** buf, int N) {
-  DtBuf* s = (DtBuf*)*buf;
-  if (s && s->N == N) return CHS_OK;
-  dt_release(s);
-  *buf = nullptr;
-  s = new (std::nothrow) DtBuf();
-  if (!s) { chs_set_error("out of host memory"); return CHS_EINVAL; }
-  *buf = s;   // (freed with its owner whatever fails below)
-  s->N = N;
+int dt_alloc(DtBuf* s) {
+  const int N = s->N;
   s->nb = (N + CHS_DT_BAND - 1) / CHS_DT_BAND;
   s->nbins = chs_distance_bins(N);
   const size_t n2 = (size_t)N * N, nc = (size_t)s->nb * N;
@@ -323,13 +304,12 @@ int dt_buffers(void** buf, int N) {
   CHS_HIP(hipMalloc(&s->out, sizeof(DtSummary)));
   CHS_HIP(hipMalloc(&s->words, sizeof(int) * DT_NW));
   CHS_HIP(hipHostMalloc((void**)&s->hRes, sizeof(DtResult), hipHostMallocDefault));
-  for (auto& e : s->ev) CHS_HIP(hipEventCreate(&e));
   return CHS_OK;
 }
 
 template <typename T>
 int launch_mask(const DtBuf* s, const void* U, double t, int side, hipStream_t st) {
-  constexpr int V = DtVec<T>::V;
+  constexpr int V = ChsVec<T>::V;
   const int N = s->N;
   // a read-once sweep: where the step loop's arrays fill the Infinity Cache it must not displace them
   const bool nt = chs_grid_exceeds_cache((size_t)N, sizeof(T));
@@ -348,7 +328,7 @@ int launch_mask(const DtBuf* s, const void* U, double t, int side, hipStream_t s
 
 int dt_run(DtBuf* s, Engine* E, hipStream_t st, double t, int side, const std::string& who) {
   const int N = s->N, n2 = N * N;
-  s->have = false; s->ms = -1.0;
+  look_forget(s);
   CHS_HIP(hipMemsetAsync(s->words, 0, sizeof(int) * DT_NW, st));
   CHS_HIP(hipMemsetAsync(s->hist, 0, sizeof(dt_u64) * (size_t)s->nbins, st));
   CHS_HIP(hipEventRecord(s->ev[0], st));
@@ -373,11 +353,7 @@ int dt_run(DtBuf* s, Engine* E, hipStream_t st, double t, int side, const std::s
     chs_set_error(who + ": self-check failed:" + m);
     return CHS_ECHECK;
   }
-  float ms = 0.f;
-  CHS_HIP(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-  s->ms = ms;
-  s->have = true;
-  return CHS_OK;
+  return look_end(s);
 }
 }  // namespace
 
@@ -388,21 +364,16 @@ void chs_dt_free(void** buf) {
 }
 
 void chs_dt_forget(void* buf) {
-  if (!buf) return;
-  DtBuf* s = (DtBuf*)buf;
-  s->have = false; s->ms = -1.0;
+  if (buf) look_forget((DtBuf*)buf);
 }
 
 int chs_dt_look(Engine* E, hipStream_t st, void** buf, double threshold, int32_t side, int64_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
-  if (!std::isfinite(threshold)) { chs_set_error(who + ": the threshold must be finite"); return CHS_EINVAL; }
-  if (side != CHS_CC_BELOW && side != CHS_CC_ABOVE) { chs_set_error(who + ": the side is CHS_CC_BELOW (0) or CHS_CC_ABOVE (1)"); return CHS_EINVAL; }
-  if (E->N > DT_MAX_N) { chs_set_error(who + ": N above " + std::to_string(DT_MAX_N)); return CHS_EINVAL; }
-  if (!E->have_U) { chs_set_error(who + ": no field (chs_set_U / chs_init_U_pcg64 first)"); return CHS_ESTATE; }
-  CHS_HIP(hipSetDevice(E->hc.device));
   int rc;
-  if ((rc = dt_buffers(buf, E->N))) return rc;
+  if ((rc = look_check_args(out, threshold, who))) return rc;
+  if (side != CHS_CC_BELOW && side != CHS_CC_ABOVE) { chs_set_error(who + ": the side is CHS_CC_BELOW (0) or CHS_CC_ABOVE (1)"); return CHS_EINVAL; }
+  if ((rc = look_check_field(E, DT_MAX_N, who))) return rc;
+  if ((rc = look_buffers<DtBuf>(buf, E->N, dt_alloc, dt_release))) return rc;
   DtBuf* s = (DtBuf*)*buf;
   if ((rc = dt_run(s, E, st, threshold, side, who))) return rc;
   memcpy(out, &s->hRes->out, sizeof(int64_t) * CHS_DT_WORDS);
@@ -411,25 +382,19 @@ int chs_dt_look(Engine* E, hipStream_t st, void** buf, double threshold, int32_t
 
 int chs_dt_hist(void* buf, int device, hipStream_t st, int32_t nbins, int64_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
   const DtBuf* s = (const DtBuf*)buf;
-  if (!s || !s->have) { chs_set_error(who + ": no look so far"); return CHS_ESTATE; }
+  int rc;
+  if ((rc = look_ready(s, out, who))) return rc;
   if (nbins != s->nbins) { chs_set_error(who + ": nbins = " + std::to_string(nbins) + ", expected " + std::to_string(s->nbins)); return CHS_EINVAL; }
-  CHS_HIP(hipSetDevice(device));
-  CHS_HIP(hipMemcpyAsync(out, s->hist, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost, st));
-  CHS_HIP(hipStreamSynchronize(st));
-  return CHS_OK;
+  return look_fetch(device, st, out, s->hist, sizeof(int64_t) * (size_t)nbins);
 }
 
 int chs_dt_map(void* buf, int device, hipStream_t st, int32_t* out, const char* who_) {
   const std::string who(who_);
-  if (!out) { chs_set_error(who + ": null argument"); return CHS_EINVAL; }
   const DtBuf* s = (const DtBuf*)buf;
-  if (!s || !s->have) { chs_set_error(who + ": no look so far"); return CHS_ESTATE; }
-  CHS_HIP(hipSetDevice(device));
-  CHS_HIP(hipMemcpyAsync(out, s->D2, sizeof(int32_t) * (size_t)s->N * s->N, hipMemcpyDeviceToHost, st));
-  CHS_HIP(hipStreamSynchronize(st));
-  return CHS_OK;
+  int rc;
+  if ((rc = look_ready(s, out, who))) return rc;
+  return look_fetch(device, st, out, s->D2, sizeof(int32_t) * (size_t)s->N * s->N);
 }
 
 extern "C" int32_t chs_distance_bins(int32_t N) {
@@ -460,12 +425,7 @@ extern "C" int chs_distance_map(chs_handle h, int32_t* out) {
 }
 
 extern "C" int chs_distance_last_ms(chs_handle h, double* ms) {
-  Engine* E = (Engine*)h;
-  if (!E || !ms) { chs_set_error("chs_distance_last_ms: null argument"); return CHS_EINVAL; }
-  const DtBuf* s = (const DtBuf*)E->dt;
-  if (!s || s->ms < 0.0) { chs_set_error("chs_distance_last_ms: no chs_distance call so far"); return CHS_ESTATE; }
-  *ms = s->ms;
-  return CHS_OK;
+  return look_last_ms(h, h ? (const DtBuf*)((Engine*)h)->dt : nullptr, ms, "chs_distance");
 }
 
 extern "C" int chs_distance_tile(int32_t* band_rows, int32_t* row_chunk) {

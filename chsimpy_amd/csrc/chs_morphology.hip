@@ -14,11 +14,9 @@
 // tile, plus one halo row per wavefront (TR / 4 + 1 rows read for TR / 4).  The four masks are classified as bit
 // slices, a popcount per class and row; the 32-bit counters of a lane are added over the wavefront, the wavefronts'
 // in LDS, and one [CHS_MORPH_WORDS] int64 partial per tile goes to HBM.  k_morph_fin adds the tiles.
-#include <cmath>
 #include <cstring>
-#include <new>
 
-#include "chs_common.h"
+#include "chs_look.h"
 
 #define MORPH_THREADS 256
 #define MORPH_WAVES (MORPH_THREADS / CHS_WAVE)
@@ -27,8 +25,6 @@
 #define MORPH_RW (MORPH_TR / MORPH_WAVES)
 #define MORPH_NCNT 6                      // counters of a lane: Q1, Q2 + QD, QD, Q3, Q4, border
 
-typedef double morph_d2 __attribute__((ext_vector_type(2)));
-typedef float morph_f4 __attribute__((ext_vector_type(4)));
 typedef long long morph_i64;
 static_assert(sizeof(morph_i64) == sizeof(int64_t), "the result words are int64");
 
@@ -40,36 +36,20 @@ struct MorphMember {
   int pad_;
 };
 
-// The field's address comes out of a record in memory, where the compiler knows nothing of it and would load through
-// flat instructions -- which count as LDS traffic too, so that every wait for a cross-lane move would wait for the row
-// on its way as well.  It is device memory: say so.
-#define MORPH_GLOBAL __attribute__((address_space(1)))
-
-template <typename T> struct MorphVec;
-template <> struct MorphVec<double> { typedef morph_d2 type; static constexpr int V = 2; };
-template <> struct MorphVec<float> { typedef morph_f4 type; static constexpr int V = 4; };
-
 // Row i of the field, the tile's MORPH_TC columns from j0 on: x[c][k] = U[i][j0 + (64 c + lane) V + k] and
 // h = U[i][j0 - 1].  No branch guards a load: a row or a column outside the grid is clamped to the nearest one inside
 // -- a load more of a cache line that is read anyway -- and the caller masks what it stands for, so that the loop around
 // is straight-line code and the next row's loads stay in flight behind the counted waits for this row's.
 template <typename T, int V, bool NT>
-__device__ __forceinline__ void morph_load(const T MORPH_GLOBAL* U, int N, int i, int j0, int lane,
+__device__ __forceinline__ void morph_load(const T CHS_GLOBAL* U, int N, int i, int j0, int lane,
                                            T (&x)[MORPH_TC / (CHS_WAVE * V)][V], T& h) {
-  typedef const typename MorphVec<T>::type MORPH_GLOBAL* VP;
   constexpr int CHUNK = CHS_WAVE * V, NCH = MORPH_TC / CHUNK;
-  const T MORPH_GLOBAL* row = U + (size_t)(i < 0 ? 0 : (i < N ? i : N - 1)) * N;
+  const T CHS_GLOBAL* row = U + (size_t)(i < 0 ? 0 : (i < N ? i : N - 1)) * N;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     int j = j0 + c * CHUNK + lane * V;
     j = j < N ? j : N - V;   // (V > 1: N is a multiple of V and so is j -- j < N is j + V - 1 < N -- and every row starts aligned)
-    if constexpr (V == 1) {
-      x[c][0] = NT ? __builtin_nontemporal_load(row + j) : row[j];
-    } else {
-      const typename MorphVec<T>::type v = NT ? __builtin_nontemporal_load(reinterpret_cast<VP>(row + j)) : *reinterpret_cast<VP>(row + j);
-#pragma unroll
-      for (int k = 0; k < V; ++k) x[c][k] = v[k];
-    }
+    chs_load<T, V, NT>(row + j, x[c]);
   }
   // The halo pixel has one address for the wavefront, which the compiler would fetch with a scalar load; scalar loads
   // share their counter with the cross-lane moves, whose waits would then wait for the next row's halo.  A vector load.
@@ -90,7 +70,7 @@ __global__ __launch_bounds__(MORPH_THREADS) void k_morph_quads(const MorphMember
 #pragma unroll
   for (int c = 0; c < NCH; ++c) k0 |= 1u << (c * V);
   const MorphMember m = mem[blockIdx.z];
-  const T MORPH_GLOBAL* U = (const T MORPH_GLOBAL*)m.U;
+  const T CHS_GLOBAL* U = (const T CHS_GLOBAL*)m.U;
   const double t = m.threshold;
   const int lane = threadIdx.x & (CHS_WAVE - 1), wave = chs_wave_id();   // (an SGPR: the row loop's branches are scalar)
   const int i0 = blockIdx.y * MORPH_TR + wave * MORPH_RW, j0 = blockIdx.x * MORPH_TC;
@@ -252,7 +232,7 @@ int morph_buffers(void** buf, int B, int N) {
 
 template <typename T>
 int launch_quads(const MorphBuf* s, hipStream_t st) {
-  constexpr int V = MorphVec<T>::V;
+  constexpr int V = ChsVec<T>::V;
   const dim3 grid(s->tx, s->ty, s->B);
   // a read-once sweep: where the step loop's arrays fill the Infinity Cache it must not displace them
   const bool nt = chs_grid_exceeds_cache((size_t)s->N, sizeof(T));

@@ -22,7 +22,7 @@
 #include <cstring>
 #include <new>
 
-#include "chs_common.h"
+#include "chs_look.h"
 #include "chs_nat_batch.h"
 
 #define SPEC_THREADS 256
@@ -30,9 +30,6 @@
 #define SPEC_TR 32                      // rows of a tile: SPEC_TR / SPEC_WAVES per wavefront
 #define SPEC_TC 512                     // columns of a tile
 #define SPEC_WIN (SPEC_TC + SPEC_TR)    // bins of a tile's window (>= sqrt(SPEC_TR^2 + SPEC_TC^2) + 2)
-
-typedef double spec_d2 __attribute__((ext_vector_type(2)));
-typedef float spec_f4 __attribute__((ext_vector_type(4)));
 
 // The bin of mode (i, j).  The float square root is a first guess only (off by one at the most for N <= 16384);
 // the two integer comparisons decide.
@@ -58,10 +55,6 @@ struct SpecMember {
   const DevState* st;  // st->meanU: the mean of U
 };
 
-template <typename T> struct SpecVec;
-template <> struct SpecVec<double> { typedef spec_d2 type; static constexpr int V = 2; };
-template <> struct SpecVec<float> { typedef spec_f4 type; static constexpr int V = 4; };
-
 // work <- U - mean(U).  V elements (16 bytes) per thread where N * N is a multiple of V, else one.
 template <typename T, int V>
 __global__ __launch_bounds__(SPEC_THREADS) void k_spec_center(const SpecMember* __restrict__ mem, size_t total) {
@@ -74,7 +67,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spec_center(const SpecMember* 
   if constexpr (V == 1) {
     *w = (T)((double)*u - mean);
   } else {
-    typedef typename SpecVec<T>::type VT;
+    typedef typename ChsVec<T>::type VT;
     const VT x = *reinterpret_cast<const VT*>(u);
     VT y;
 #pragma unroll
@@ -100,7 +93,7 @@ template <typename T, int V, bool NT>
 __global__ __launch_bounds__(SPEC_THREADS) void k_spec_bins(const SpecMember* __restrict__ mem, int N,
                                                              double* __restrict__ part) {
   __shared__ double acc[SPEC_WAVES][SPEC_WIN];
-  typedef typename SpecVec<T>::type VT;
+  typedef typename ChsVec<T>::type VT;
   constexpr int CHUNK = CHS_WAVE * V;        // columns of one load of a wavefront
   constexpr int NCH = SPEC_TC / CHUNK;
   const T* __restrict__ C = (const T*)mem[blockIdx.z].coef;
@@ -275,7 +268,7 @@ int transform_one(Engine* E) {
 template <typename T>
 int launch_center(const SpecBuf* s, hipStream_t st) {
   const size_t total = (size_t)s->N * s->N;
-  constexpr int V = SpecVec<T>::V;
+  constexpr int V = ChsVec<T>::V;
   if (total % V == 0) {
     const size_t threads = total / V;
     k_spec_center<T, V><<<dim3((unsigned)((threads + SPEC_THREADS - 1) / SPEC_THREADS), s->B), SPEC_THREADS, 0, st>>>(s->mem, total);
@@ -288,7 +281,7 @@ int launch_center(const SpecBuf* s, hipStream_t st) {
 
 template <typename T>
 int launch_bins(const SpecBuf* s, hipStream_t st) {
-  constexpr int V = SpecVec<T>::V;
+  constexpr int V = ChsVec<T>::V;
   const dim3 grid(s->tx, s->ty, s->B);
   // a read-once sweep: where the step loop's arrays fill the Infinity Cache it must not displace them
   const bool nt = chs_grid_exceeds_cache((size_t)s->N, sizeof(T));

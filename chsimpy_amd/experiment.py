@@ -17,6 +17,7 @@ results do not depend on how many ranks share the work.
 import argparse
 import os
 import threading
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -125,7 +126,7 @@ def _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess):
 
 def _domain_row(sf):
     """(k1, ell, ell_phys) of a member's final field (chsimpy_amd.spectrum.StructureFactor)."""
-    return (sf.k1, sf.ell, sf.ell_phys)
+    return (float(sf.k1), float(sf.ell), float(sf.ell_phys))
 
 
 def _morphology_row(mo):
@@ -176,30 +177,119 @@ def _chords_of(solver):
     return row
 
 
+DOMAINS_COLS = ('id', 'k1', 'ell', 'ell_phys')
+MORPHOLOGY_COLS = ('id', 'threshold', 'n_A', 'SA', 'perimeter', 'perimeter_inner', 'euler8', 'euler4')
+DROPLETS_COLS = ('id', 'threshold', 'connectivity', 'count_below', 'largest_below', 'spanning_below', 'mean_area_below',
+                 'count_above', 'largest_above', 'spanning_above', 'mean_area_above')
+WIDTHS_COLS = ('id', 'threshold') + tuple(f"{k}_{side}" for side in ('below', 'above')
+                                          for k in ('fg', 'r_max', 'r2_mean', 'r_floor_mean', 'q50', 'q90'))
+CHORDS_COLS = ('id', 'threshold') + tuple(f"{k}_{phase}_{d}" for phase in ('below', 'above') for d in ('rows', 'cols')
+                                          for k in ('count', 'mean', 'mean_weighted', 'max', 'cut'))
+
+
+# `--dry-run`: rows made up from the run id, as the members' records are (_dry_member) -- members without device work
+def _dry_domains(i, p, opts):
+    return (1.0 + i, 2.0 * p.N / (1.0 + i), 2.0 * p.N / (1.0 + i) * p.L / (p.N - 1))
+
+
+def _dry_morphology(i, p, opts):
+    """A full field with i single-pixel holes."""
+    return (float(p.threshold), p.N * p.N - i, (p.N * p.N - i) / (p.N * p.N), 4 * p.N + 4 * i, 4 * i, 1 - i, 1 - i)
+
+
+def _dry_droplets(i, p, opts):
+    """i + 1 droplets of 3 pixels in a spanning matrix with i holes."""
+    return (float(p.threshold), opts['droplets_connectivity'], i + 1, 3, 0, 3.0, 1, p.N * p.N - 3 * (i + 1), 1,
+            float(p.N * p.N - 3 * (i + 1)))
+
+
+def _dry_widths(i, p, opts):
+    """i + 1 pixels below, each its own distance 1; a matrix i + 2 wide."""
+    return (float(p.threshold), i + 1, 1.0, 1.0, 1.0, 1, 1,
+            p.N * p.N - (i + 1), float(i + 2), 0.5 * (i + 2) ** 2, 0.5 * (i + 2), (i + 2) // 2, i + 2)
+
+
+def _dry_chords(i, p, opts):
+    """i + 1 inner chords of 2 and 4 pixels below along the rows, ..."""
+    return (float(p.threshold), i + 1, 3.0, 10.0 / 3.0, 4, 1, i + 2, 1.5, 1.75, 2, 0,
+            i + 3, float(i + 2), i + 2.5, 2 * i + 4, p.N, i + 4, 0.1 * (i + 1), 1.0 / (i + 3), i + 5, p.N + 1)
+
+
+class Measurement(NamedTuple):
+    """One look at a member's final field, measured on the device behind its run: the keyword of the run functions under
+    which its rows are collected (a dict, run id -> the values behind the id), the command-line flag, the file
+    ``<file_id>-<suffix>.csv`` with its columns (``int_cols`` of them written as integers), and where a row comes from:
+    ``row_of(solver, opts)`` of one member, ``rows_of_batch(bs)`` where one device pass serves a whole BatchSolver, and
+    ``dry_row(i, p, opts)`` of a `--dry-run`.  ``opts``: {'droplets_connectivity': 4 or 8}."""
+    key: str
+    flag: str
+    help: str
+    suffix: str
+    cols: tuple
+    int_cols: frozenset
+    row_of: Callable
+    dry_row: Callable
+    rows_of_batch: Optional[Callable] = None
+
+
+# In the order in which the files are written and printed.
+MEASUREMENTS = (
+    Measurement('domains', '--domain-size', 'measure every member\'s domain size on the device behind its run (radially '
+                'averaged structure factor of the final field): <id>-domains.csv with id, k1, ell, ell_phys',
+                'domains', DOMAINS_COLS, frozenset({'id'}),
+                lambda s, opts: _domain_row(s.structure_factor()), _dry_domains,
+                lambda bs: [_domain_row(sf) for sf in bs.structure_factor()]),
+    Measurement('morphology', '--morphology', 'measure the morphology of every member\'s final field on the device behind '
+                'its run (bit-quad counts of the field below the threshold): <id>-morphology.csv with id, threshold, n_A, '
+                'SA, perimeter, perimeter_inner, euler8, euler4',
+                'morphology', MORPHOLOGY_COLS,
+                frozenset({'id', 'n_A', 'perimeter', 'perimeter_inner', 'euler8', 'euler4'}),
+                lambda s, opts: _morphology_row(s.morphology()), _dry_morphology,
+                lambda bs: [_morphology_row(mo) for mo in bs.morphology()]),
+    Measurement('droplets', '--droplets', 'label the connected components of every member\'s final field on the device '
+                'behind its run, on both sides of the threshold: <id>-droplets.csv with id, threshold, connectivity, and '
+                'count, largest, spanning, mean_area below and above',
+                'droplets', DROPLETS_COLS,
+                frozenset({'id', 'connectivity', 'count_below', 'largest_below', 'spanning_below', 'count_above', 'largest_above',
+                           'spanning_above'}),
+                lambda s, opts: _droplets_of(s, opts['droplets_connectivity']), _dry_droplets),
+    Measurement('widths', '--widths', 'measure the exact Euclidean distance transform of every member\'s final field on the '
+                'device behind its run, on both sides of the threshold: <id>-widths.csv with id, threshold, and fg, r_max, '
+                'r2_mean, r_floor_mean, q50, q90 (radius-bin quantiles) below and above',
+                'widths', WIDTHS_COLS,
+                frozenset({'id', 'fg_below', 'q50_below', 'q90_below', 'fg_above', 'q50_above', 'q90_above'}),
+                lambda s, opts: _widths_of(s), _dry_widths),
+    Measurement('chords', '--chords', 'measure the chord lengths (linear intercepts) of both phases of every member\'s final '
+                'field on the device behind its run, along rows and columns: <id>-chords.csv with id, threshold, and count, '
+                'mean, mean_weighted, max (inner chords), cut (chords at a wall) for below/above x rows/cols',
+                'chords', CHORDS_COLS,
+                frozenset(c for c in CHORDS_COLS if c == 'id' or c.split('_')[0] in ('count', 'max', 'cut')),
+                lambda s, opts: _chords_of(s), _dry_chords),
+)
+
+
+def _asked(domains, morphology, droplets, widths, chords):
+    """The measurements a caller asked for, keyed like MEASUREMENTS: the dicts its rows go to."""
+    given = dict(domains=domains, morphology=morphology, droplets=droplets, widths=widths, chords=chords)
+    return {k: v for k, v in given.items() if v is not None}
+
+
 def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None,
                        morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None):
-    """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains`` (a dict): the
-    member's domain size, measured on the device behind its run, goes to ``domains[run_id]``; ``morphology`` (a dict):
-    likewise the morphology of its final field at ``params.threshold``; ``droplets`` (a dict): likewise its connected
-    components on both sides of that threshold (summary-only looks, ``droplets_connectivity`` 4 or 8); ``widths`` (a
-    dict): likewise the distance transform on both sides of it (widest point, mean squared radius, radius-bin mean and
-    quantiles); ``chords`` (a dict): likewise the chord lengths of both phases along rows and columns (one summary-only
-    look)."""
+    """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains``, ``morphology``,
+    ``droplets``, ``widths``, ``chords`` (a dict each): the member's row of that entry of MEASUREMENTS, measured on the
+    device behind its run at ``params.threshold``, goes to ``<dict>[run_id]`` (``droplets_connectivity`` 4 or 8: that of
+    the droplets)."""
     from .simulator import Simulator
+    asked = _asked(domains, morphology, droplets, widths, chords)
+    opts = {'droplets_connectivity': droplets_connectivity}
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
     try:
         solution = simulator.solve()
-        if domains is not None:
-            domains[run_id] = _domain_row(simulator.solver.structure_factor())
-        if morphology is not None:
-            morphology[run_id] = _morphology_row(simulator.solver.morphology())
-        if droplets is not None:
-            droplets[run_id] = _droplets_of(simulator.solver, droplets_connectivity)
-        if widths is not None:
-            widths[run_id] = _widths_of(simulator.solver)
-        if chords is not None:
-            chords[run_id] = _chords_of(simulator.solver)
+        for m in MEASUREMENTS:
+            if m.key in asked:
+                asked[m.key][run_id] = m.row_of(simulator.solver, opts)
         simulator.export()
         rec = _member_record(run_id, params, solution, fac_A0, fac_A1, postprocess)
     finally:
@@ -212,31 +302,22 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
                   morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
-    members run as a seat queue, that many at a time (None: all of them from the first step on).  ``domains``,
-    ``morphology``: as in run_experiment_gpu, each from one device pass over the group; ``droplets``, ``widths``, ``chords``:
-    as there, member by member on the batch's stream."""
+    members run as a seat queue, that many at a time (None: all of them from the first step on).  The measurements: as
+    in run_experiment_gpu, from one device pass over the group where the entry has ``rows_of_batch``, else member by
+    member on the batch's stream."""
     from .batch import BatchSolver
     from .simulator import Simulator
+    asked = _asked(domains, morphology, droplets, widths, chords)
+    opts = {'droplets_connectivity': droplets_connectivity}
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
     bs = BatchSolver([r[0] for r in runs], U_init, seats=seats)
     try:
         bs.prepare()
         solutions = bs.solve_or_resume()
-        if domains is not None:
-            for i, sf in zip(run_ids, bs.structure_factor()):
-                domains[i] = _domain_row(sf)
-        if morphology is not None:
-            for i, mo in zip(run_ids, bs.morphology()):
-                morphology[i] = _morphology_row(mo)
-        if droplets is not None:
-            for i, s in zip(run_ids, bs.solvers):
-                droplets[i] = _droplets_of(s, droplets_connectivity)
-        if widths is not None:
-            for i, s in zip(run_ids, bs.solvers):
-                widths[i] = _widths_of(s)
-        if chords is not None:
-            for i, s in zip(run_ids, bs.solvers):
-                chords[i] = _chords_of(s)
+        for m in MEASUREMENTS:
+            if m.key in asked:
+                rows = m.rows_of_batch(bs) if m.rows_of_batch else (m.row_of(s, opts) for s in bs.solvers)
+                asked[m.key].update(zip(run_ids, rows))
         recs = []
         for m, (i, (params, fac_A0, fac_A1)) in enumerate(zip(run_ids, runs)):
             # Simulator.export() of the member (simulator.py:135-156), without a Solver of its own
@@ -255,189 +336,55 @@ def my_run_ids(nr_items, rank, world):
     return [i for i in range(nr_items) if i % world == rank]
 
 
+def _all_gather_rows(rows, ncols, id_col, nr_items, world, dist, device):
+    """Every rank's rows, as tuples of floats: one all_gather of a (ceil(n/world), ncols) float64 block per rank -- a few
+    KiB; latency-bound, bandwidth irrelevant.  A block is padded with NaN rows, recognised by their id column alone
+    (other columns may hold NaN in a member's row)."""
+    import torch
+    per = (nr_items + world - 1) // world
+    buf = torch.full((per, ncols), float('nan'), dtype=torch.float64, device=device)
+    for k, row in enumerate(rows):
+        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
+    out = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(out, buf)
+    return [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[id_col])]
+
+
 def gather_records(local, nr_items, rank, world, dist=None, device='cpu'):
-    """All per-run records on every rank, ordered by run id.  One all_gather of a
-    (ceil(n/world), 12) float64 block per rank -- a few KiB; latency-bound, bandwidth irrelevant."""
-    if world == 1 or dist is None:
-        return sorted(local, key=lambda r: r[9])
-    import torch
-    per = (nr_items + world - 1) // world
-    buf = torch.full((per, len(COLS)), float('nan'), dtype=torch.float64, device=device)
-    for i, rec in enumerate(local):
-        buf[i] = torch.tensor([float(x) for x in rec], dtype=torch.float64, device=device)
-    out = [torch.empty_like(buf) for _ in range(world)]
-    dist.all_gather(out, buf)
-    recs = []
-    for t in out:
-        for row in t.cpu().numpy():
-            if not np.isnan(row[9]):
-                recs.append(tuple(row.tolist()))
-    return sorted(recs, key=lambda r: r[9])
+    """All per-run records on every rank, ordered by run id."""
+    if world > 1 and dist is not None:
+        local = _all_gather_rows(local, len(COLS), 9, nr_items, world, dist, device)
+    return sorted(local, key=lambda r: r[9])
 
 
-def gather_domains(local, nr_items, rank, world, dist=None, device='cpu'):
-    """The members' (id, k1, ell, ell_phys) on every rank, ordered by run id: `local` maps this rank's run ids to
-    (k1, ell, ell_phys).  One all_gather of a (ceil(n/world), 4) float64 block per rank, as gather_records."""
-    rows = [(i,) + tuple(float(x) for x in v) for i, v in sorted(local.items())]
-    if world == 1 or dist is None:
-        return rows
-    import torch
-    per = (nr_items + world - 1) // world
-    buf = torch.full((per, 4), float('nan'), dtype=torch.float64, device=device)
-    for k, row in enumerate(rows):
-        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
-    out = [torch.empty_like(buf) for _ in range(world)]
-    dist.all_gather(out, buf)
-    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
-    return sorted((int(r[0]),) + r[1:] for r in got)
-
-
-MORPHOLOGY_COLS = ('id', 'threshold', 'n_A', 'SA', 'perimeter', 'perimeter_inner', 'euler8', 'euler4')
-
-
-def gather_morphology(local, nr_items, rank, world, dist=None, device='cpu'):
-    """The members' MORPHOLOGY_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the seven
-    values behind the id.  One all_gather of a (ceil(n/world), 8) float64 block per rank, as gather_domains (the counts
-    are integers below 2^53: exact in float64)."""
+def gather_rows(local, ncols, nr_items, rank, world, dist=None, device='cpu'):
+    """The members' rows of one measurement on every rank, ordered by run id: `local` maps this rank's run ids to the
+    ``ncols - 1`` values behind the id (the counts are integers below 2^53: exact in the float64 block)."""
     rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
     if world == 1 or dist is None:
         return rows
-    import torch
-    per = (nr_items + world - 1) // world
-    buf = torch.full((per, len(MORPHOLOGY_COLS)), float('nan'), dtype=torch.float64, device=device)
-    for k, row in enumerate(rows):
-        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
-    out = [torch.empty_like(buf) for _ in range(world)]
-    dist.all_gather(out, buf)
-    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
+    got = _all_gather_rows(rows, ncols, 0, nr_items, world, dist, device)
     return sorted((int(r[0]),) + r[1:] for r in got)
 
 
-DROPLETS_COLS = ('id', 'threshold', 'connectivity', 'count_below', 'largest_below', 'spanning_below', 'mean_area_below',
-                 'count_above', 'largest_above', 'spanning_above', 'mean_area_above')
-
-
-def gather_droplets(local, nr_items, rank, world, dist=None, device='cpu'):
-    """The members' DROPLETS_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the ten values
-    behind the id.  One all_gather of a float64 block per rank, as gather_morphology (the counts are integers below
-    2^53: exact in float64)."""
-    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
-    if world == 1 or dist is None:
-        return rows
-    import torch
-    per = (nr_items + world - 1) // world
-    buf = torch.full((per, len(DROPLETS_COLS)), float('nan'), dtype=torch.float64, device=device)
-    for k, row in enumerate(rows):
-        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
-    out = [torch.empty_like(buf) for _ in range(world)]
-    dist.all_gather(out, buf)
-    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
-    return sorted((int(r[0]),) + r[1:] for r in got)
-
-
-def write_droplets(file_id, rows):
-    """``<file_id>-droplets.csv``: DROPLETS_COLS per member (--droplets), the counts as integers, the floats written so
-    that they read back exactly."""
-    name = f"{file_id}-droplets.csv"
-    with open(name, 'w') as f:
-        f.write(','.join(DROPLETS_COLS) + "\n")
-        for i, t, conn, cb, lb, sb, mb, ca, la, sa, ma in rows:
-            f.write(f"{int(i)},{float(t)!r},{int(conn)},{int(cb)},{int(lb)},{int(sb)},{float(mb)!r},"
-                    f"{int(ca)},{int(la)},{int(sa)},{float(ma)!r}\n")
-    return name
-
-
-WIDTHS_COLS = ('id', 'threshold') + tuple(f"{k}_{side}" for side in ('below', 'above')
-                                          for k in ('fg', 'r_max', 'r2_mean', 'r_floor_mean', 'q50', 'q90'))
-
-
-def gather_widths(local, nr_items, rank, world, dist=None, device='cpu'):
-    """The members' WIDTHS_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the thirteen
-    values behind the id.  One all_gather of a float64 block per rank, as gather_droplets (the counts are integers below
-    2^53: exact in float64; a side without a finite distance has NaN there, which only the id column is tested for)."""
-    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
-    if world == 1 or dist is None:
-        return rows
-    import torch
-    per = (nr_items + world - 1) // world
-    buf = torch.full((per, len(WIDTHS_COLS)), float('nan'), dtype=torch.float64, device=device)
-    for k, row in enumerate(rows):
-        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
-    out = [torch.empty_like(buf) for _ in range(world)]
-    dist.all_gather(out, buf)
-    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
-    return sorted((int(r[0]),) + r[1:] for r in got)
-
-
-def write_widths(file_id, rows):
-    """``<file_id>-widths.csv``: WIDTHS_COLS per member (--widths), the counts and quantiles as integers, the floats
+def write_rows(file_id, measurement, rows):
+    """``<file_id>-<suffix>.csv``: the measurement's columns per member, its integer columns as integers, the floats
     written so that they read back exactly."""
-    name = f"{file_id}-widths.csv"
+    name = f"{file_id}-{measurement.suffix}.csv"
     with open(name, 'w') as f:
-        f.write(','.join(WIDTHS_COLS) + "\n")
+        f.write(','.join(measurement.cols) + "\n")
         for row in rows:
-            i, t, sides = row[0], row[1], (row[2:8], row[8:14])
-            f.write(f"{int(i)},{float(t)!r}" + ''.join(
-                f",{int(fg)},{float(rm)!r},{float(r2)!r},{float(rf)!r},{int(q50)},{int(q90)}"
-                for fg, rm, r2, rf, q50, q90 in sides) + "\n")
+            f.write(','.join(str(int(x)) if c in measurement.int_cols else repr(float(x))
+                             for c, x in zip(measurement.cols, row)) + "\n")
     return name
 
 
-CHORDS_COLS = ('id', 'threshold') + tuple(f"{k}_{phase}_{d}" for phase in ('below', 'above') for d in ('rows', 'cols')
-                                          for k in ('count', 'mean', 'mean_weighted', 'max', 'cut'))
+def _writer(measurement):
+    return lambda file_id, rows: write_rows(file_id, measurement, rows)
 
 
-def gather_chords(local, nr_items, rank, world, dist=None, device='cpu'):
-    """The members' CHORDS_COLS on every rank, ordered by run id: `local` maps this rank's run ids to the twenty-one
-    values behind the id.  One all_gather of a float64 block per rank, as gather_widths (the counts are integers below
-    2^53: exact in float64; a phase without an inner chord has NaN there, which only the id column is tested for)."""
-    rows = [(i,) + tuple(v) for i, v in sorted(local.items())]
-    if world == 1 or dist is None:
-        return rows
-    import torch
-    per = (nr_items + world - 1) // world
-    buf = torch.full((per, len(CHORDS_COLS)), float('nan'), dtype=torch.float64, device=device)
-    for k, row in enumerate(rows):
-        buf[k] = torch.tensor([float(x) for x in row], dtype=torch.float64, device=device)
-    out = [torch.empty_like(buf) for _ in range(world)]
-    dist.all_gather(out, buf)
-    got = [tuple(r.tolist()) for t in out for r in t.cpu().numpy() if not np.isnan(r[0])]
-    return sorted((int(r[0]),) + r[1:] for r in got)
-
-
-def write_chords(file_id, rows):
-    """``<file_id>-chords.csv``: CHORDS_COLS per member (--chords), the counts and the longest chords as integers, the
-    floats written so that they read back exactly."""
-    name = f"{file_id}-chords.csv"
-    with open(name, 'w') as f:
-        f.write(','.join(CHORDS_COLS) + "\n")
-        for row in rows:
-            i, t, groups = row[0], row[1], [row[2 + 5 * k:7 + 5 * k] for k in range(4)]
-            f.write(f"{int(i)},{float(t)!r}" + ''.join(
-                f",{int(n)},{float(m)!r},{float(mw)!r},{int(mx)},{int(cut)}" for n, m, mw, mx, cut in groups) + "\n")
-    return name
-
-
-def write_morphology(file_id, rows):
-    """``<file_id>-morphology.csv``: MORPHOLOGY_COLS per member (--morphology), the counts as integers, the two floats
-    written so that they read back exactly."""
-    name = f"{file_id}-morphology.csv"
-    with open(name, 'w') as f:
-        f.write(','.join(MORPHOLOGY_COLS) + "\n")
-        for i, t, n_A, SA, per, per_in, e8, e4 in rows:
-            f.write(f"{int(i)},{float(t)!r},{int(n_A)},{float(SA)!r},{int(per)},{int(per_in)},{int(e8)},{int(e4)}\n")
-    return name
-
-
-def write_domains(file_id, rows):
-    """``<file_id>-domains.csv``: ``id, k1, ell, ell_phys`` per member (--domain-size), the floats written so that
-    they read back exactly."""
-    name = f"{file_id}-domains.csv"
-    with open(name, 'w') as f:
-        f.write("id,k1,ell,ell_phys\n")
-        for i, k1, ell, ell_phys in rows:
-            f.write(f"{int(i)},{float(k1)!r},{float(ell)!r},{float(ell_phys)!r}\n")
-    return name
+# the writers by the names callers know: write_widths(file_id, rows) is write_rows with the widths entry
+write_domains, write_morphology, write_droplets, write_widths, write_chords = (_writer(m) for m in MEASUREMENTS)
 
 
 def write_metadata(file_id, ep, extra=()):
@@ -485,35 +432,16 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
     into queues of at most ``queue_members``; ``batch_fn`` is called once per queue.  A chirp batch has no queue:
     ``queue`` at such an N runs member by member, with the note.
 
-    ``domains`` (a dict, with the default run functions): every member's domain size -- first moment k1 of the radially
-    averaged structure factor of its final field, the characteristic length 2N/k1 and that length in the solver's unit
-    -- is measured on the device behind its run and left in ``domains[run_id]`` for this rank's runs (gather_domains).
-
-    ``morphology`` (a dict, with the default run functions): likewise the morphology of every member's final field at
-    its ``params.threshold`` -- area, interface length, Euler numbers (chsimpy_amd/morphology.py) -- in
-    ``morphology[run_id]`` (gather_morphology).
-
-    ``droplets`` (a dict, with the default run functions): likewise the connected components of every member's final
-    field on both sides of its ``params.threshold`` -- count, largest, spanning, mean area (chsimpy_amd/components.py),
-    at ``droplets_connectivity`` -- in ``droplets[run_id]`` (gather_droplets).
-
-    ``widths`` (a dict, with the default run functions): likewise the distance transform of every member's final field
-    on both sides of its ``params.threshold`` -- foreground, widest point, mean squared radius, radius-bin mean and
-    quantiles (chsimpy_amd/distance.py) -- in ``widths[run_id]`` (gather_widths).
-
-    ``chords`` (a dict, with the default run functions): likewise the chord lengths of both phases of every member's
-    final field along rows and columns -- count, mean, weighted mean, longest inner chord and the chords at a wall
-    (chsimpy_amd/chords.py) -- in ``chords[run_id]`` (gather_chords)."""
+    ``domains``, ``morphology``, ``droplets``, ``widths``, ``chords`` (a dict each, with the default run functions): that
+    entry of MEASUREMENTS -- the domain size from the radially averaged structure factor (chsimpy_amd/spectrum.py), the
+    morphology (morphology.py), the connected components on both sides of the threshold at ``droplets_connectivity``
+    (components.py), the distance transform on both sides (distance.py), the chord lengths of both phases along rows
+    and columns (chords.py) -- is measured on every member's final field, on the device behind its run at its
+    ``params.threshold``, and left in ``<dict>[run_id]`` for this rank's runs (gather_rows)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
-    dom = {} if domains is None else {'domains': domains}   # (the run functions are called as ever without it)
-    if morphology is not None:
-        dom['morphology'] = morphology
+    dom = _asked(domains, morphology, droplets, widths, chords)   # (the run functions are called as ever without them)
     if droplets is not None:
-        dom['droplets'], dom['droplets_connectivity'] = droplets, int(droplets_connectivity)
-    if widths is not None:
-        dom['widths'] = widths
-    if chords is not None:
-        dom['chords'] = chords
+        dom['droplets_connectivity'] = int(droplets_connectivity)
     if run_fn is None:
         def run_fn(run_id, p, rv, al):
             return run_experiment_gpu(run_id, p, rv, al, U_init, **dom)
@@ -581,7 +509,7 @@ def _launch_own_ranks(a, argv):
     sys.stdout.flush()
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(description='chsimpy_amd ensemble (cf. chsimpy-experiment)')
     ap.add_argument('-N', type=int, default=512)
     ap.add_argument('-n', '--ntmax', type=int, default=int(1e6))
@@ -603,21 +531,8 @@ def main(argv=None):
                     'a member that stops hands its seat to the next one on the device')
     ap.add_argument('--queue-members', type=int, default=256, help='members of one queue at the most (each owns its device '
                     'arrays from the start)')
-    ap.add_argument('--domain-size', action='store_true', help='measure every member\'s domain size on the device behind its '
-                    'run (radially averaged structure factor of the final field): <id>-domains.csv with id, k1, ell, ell_phys')
-    ap.add_argument('--morphology', action='store_true', help='measure the morphology of every member\'s final field on the '
-                    'device behind its run (bit-quad counts of the field below the threshold): <id>-morphology.csv with id, '
-                    'threshold, n_A, SA, perimeter, perimeter_inner, euler8, euler4')
-    ap.add_argument('--droplets', action='store_true', help='label the connected components of every member\'s final field on '
-                    'the device behind its run, on both sides of the threshold: <id>-droplets.csv with id, threshold, '
-                    'connectivity, and count, largest, spanning, mean_area below and above')
-    ap.add_argument('--widths', action='store_true', help='measure the exact Euclidean distance transform of every member\'s '
-                    'final field on the device behind its run, on both sides of the threshold: <id>-widths.csv with id, '
-                    'threshold, and fg, r_max, r2_mean, r_floor_mean, q50, q90 (radius-bin quantiles) below and above')
-    ap.add_argument('--chords', action='store_true', help='measure the chord lengths (linear intercepts) of both phases of '
-                    'every member\'s final field on the device behind its run, along rows and columns: <id>-chords.csv with '
-                    'id, threshold, and count, mean, mean_weighted, max (inner chords), cut (chords at a wall) for '
-                    'below/above x rows/cols')
+    for m in MEASUREMENTS:
+        ap.add_argument(m.flag, dest=m.key, action='store_true', help=m.help)
     ap.add_argument('--droplets-connectivity', type=int, choices=(4, 8), default=4, help='the connectivity of --droplets')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
                     'such as torch.distributed.run has set RANK/WORLD_SIZE')
@@ -625,7 +540,11 @@ def main(argv=None):
                     help='torch.distributed backend: nccl (= RCCL, ranks on GPUs) or gloo (CPU rehearsal)')
     ap.add_argument('--dry-run', action='store_true', help='members without device work: rehearses launcher, partition, '
                     'core placement and the gather on CPUs; the result files are not results')
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = arg_parser().parse_args(argv)
 
     if a.gpus > 1 and 'RANK' not in os.environ:
         return _launch_own_ranks(a, argv)
@@ -669,50 +588,20 @@ def main(argv=None):
                        + ([f"batch_per_rank, {a.batch}"] if a.batch > 0 else [])
                        + ([f"queue_members, {a.queue_members}"] if (a.batch > 0 and a.queue) else [])
                        + (["dry_run, True"] if a.dry_run else []))
-    domains = {} if a.domain_size else None
-    morph = {} if a.morphology else None
-    drops = {} if a.droplets else None
-    wid = {} if a.widths else None
-    cho = {} if a.chords else None
+    asked = [m for m in MEASUREMENTS if getattr(a, m.key)]
+    local = {m.key: {} for m in asked}
+    opts = {'droplets_connectivity': a.droplets_connectivity}
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,
                            world=world, device=device, concurrent=a.concurrent, batch=max(a.batch, 0),
                            batch_fn=_dry_batch if (a.dry_run and a.batch > 0) else None,
-                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members, domains=domains,
-                           **({} if morph is None else {'morphology': morph}),
-                           **({} if drops is None else {'droplets': drops, 'droplets_connectivity': a.droplets_connectivity}),
-                           **({} if wid is None else {'widths': wid}),
-                           **({} if cho is None else {'chords': cho}))
-    if domains is not None:
+                           queue=bool(a.queue and a.batch > 0), queue_members=a.queue_members,
+                           **local, **(opts if a.droplets else {}))
+    nr = make_rand_values(ep)[2] if asked else 0
+    rows = {}
+    for m in asked:
         if a.dry_run:   # (members without device work: a function of the run id, as their records are)
-            nr = make_rand_values(ep)[2]
-            domains = {i: (1.0 + i, 2.0 * p.N / (1.0 + i), 2.0 * p.N / (1.0 + i) * p.L / (p.N - 1)) for i in my_run_ids(nr, rank, world)}
-        domain_rows = gather_domains(domains, make_rand_values(ep)[2], rank, world, dist, device)
-    if morph is not None:
-        nr = make_rand_values(ep)[2]
-        if a.dry_run:   # (made up from the run id, as above: a full field with i single-pixel holes)
-            morph = {i: (float(p.threshold), p.N * p.N - i, (p.N * p.N - i) / (p.N * p.N), 4 * p.N + 4 * i, 4 * i, 1 - i, 1 - i)
-                     for i in my_run_ids(nr, rank, world)}
-        morphology_rows = gather_morphology(morph, nr, rank, world, dist, device)
-    if drops is not None:
-        nr = make_rand_values(ep)[2]
-        if a.dry_run:   # (made up from the run id, as above: i + 1 droplets of 3 pixels in a spanning matrix with i holes)
-            drops = {i: (float(p.threshold), a.droplets_connectivity, i + 1, 3, 0, 3.0, 1, p.N * p.N - 3 * (i + 1), 1,
-                         float(p.N * p.N - 3 * (i + 1))) for i in my_run_ids(nr, rank, world)}
-        droplets_rows = gather_droplets(drops, nr, rank, world, dist, device)
-    if wid is not None:
-        nr = make_rand_values(ep)[2]
-        if a.dry_run:   # (made up from the run id, as above: i + 1 pixels below, each its own distance 1; a matrix i + 2 wide)
-            wid = {i: (float(p.threshold), i + 1, 1.0, 1.0, 1.0, 1, 1,
-                       p.N * p.N - (i + 1), float(i + 2), 0.5 * (i + 2) ** 2, 0.5 * (i + 2), (i + 2) // 2, i + 2)
-                   for i in my_run_ids(nr, rank, world)}
-        widths_rows = gather_widths(wid, nr, rank, world, dist, device)
-    if cho is not None:
-        nr = make_rand_values(ep)[2]
-        if a.dry_run:   # (made up from the run id, as above: i + 1 inner chords of 2 and 4 pixels below along the rows, ...)
-            cho = {i: (float(p.threshold), i + 1, 3.0, 10.0 / 3.0, 4, 1, i + 2, 1.5, 1.75, 2, 0,
-                       i + 3, float(i + 2), i + 2.5, 2 * i + 4, p.N, i + 4, 0.1 * (i + 1), 1.0 / (i + 3), i + 5, p.N + 1)
-                   for i in my_run_ids(nr, rank, world)}
-        chords_rows = gather_chords(cho, nr, rank, world, dist, device)
+            local[m.key] = {i: m.dry_row(i, p, opts) for i in my_run_ids(nr, rank, world)}
+        rows[m.key] = gather_rows(local[m.key], len(m.cols), nr, rank, world, dist, device)
     if rank == 0:
         df, agg = write_results(p.file_id, records)
         print(agg.T)
@@ -720,16 +609,8 @@ def main(argv=None):
         print(f"  {p.file_id}-metadata.csv")
         print(f"  {p.file_id}-results-agg.csv")
         print(f"  {p.file_id}-results.csv")
-        if domains is not None:
-            print(f"  {write_domains(p.file_id, domain_rows)}")
-        if morph is not None:
-            print(f"  {write_morphology(p.file_id, morphology_rows)}")
-        if drops is not None:
-            print(f"  {write_droplets(p.file_id, droplets_rows)}")
-        if wid is not None:
-            print(f"  {write_widths(p.file_id, widths_rows)}")
-        if cho is not None:
-            print(f"  {write_chords(p.file_id, chords_rows)}")
+        for m in asked:
+            print(f"  {write_rows(p.file_id, m, rows[m.key])}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

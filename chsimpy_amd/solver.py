@@ -157,13 +157,17 @@ class Solver:
             sol.__dict__['_U_dirty'] = False
             sol.__dict__['_U_print'] = _fingerprint(u)   # (the array mirrors the device field again: a later edit is noticed)
 
+    def _look_engine(self):
+        """The opening of a look: the engine, with a field the host edited pushed to the device."""
+        eng = self._get_engine()
+        self._push_edited_U()
+        return eng
+
     def structure_factor(self):
         """The radially averaged structure factor of the field the device holds, a `spectrum.StructureFactor`
         (Ssum, n, S, k1, ell, ell_phys).  Computed on the device between two calls without changing the run; a field
         the host edited is pushed first, as solve_or_resume does.  Needs a field: prepare() first."""
-        eng = self._get_engine()
-        self._push_edited_U()
-        return spectrum.StructureFactor(eng.structure_factor(), self.params.N, self.solution.delx)
+        return spectrum.StructureFactor(self._look_engine().structure_factor(), self.params.N, self.solution.delx)
 
     def morphology(self, threshold=None):
         """Area, interface length and Euler number of the field the device holds, thresholded at `threshold` (None:
@@ -171,8 +175,7 @@ class Solver:
         between two calls, which the run does not notice.  A field the host edited is pushed first, as solve_or_resume
         does.  Needs a field: prepare() first."""
         t = float(self.params.threshold if threshold is None else threshold)
-        eng = self._get_engine()
-        self._push_edited_U()
+        eng = self._look_engine()
         return morphology.Morphology(eng.morphology(t), self.params.N, t, self.solution.delx)
 
     def components(self, threshold=None, connectivity=4, side='below', table=True, labels=False):
@@ -184,8 +187,7 @@ class Solver:
         edited is pushed first, as solve_or_resume does.  Needs a field: prepare() first."""
         t = float(self.params.threshold if threshold is None else threshold)
         conn, code = components.check_connectivity(connectivity), components.side_code(side)
-        eng = self._get_engine()
-        self._push_edited_U()
+        eng = self._look_engine()
         words, tab, lab = eng.components_look(t, conn, code, table, labels)
         return components.Components(words, self.params.N, t, conn, code, table=tab, labels=lab, delx=self.solution.delx)
 
@@ -199,8 +201,7 @@ class Solver:
         does.  Needs a field: prepare() first."""
         t = float(self.params.threshold if threshold is None else threshold)
         code = distance.side_code(side)
-        eng = self._get_engine()
-        self._push_edited_U()
+        eng = self._look_engine()
         words, hi, d2 = eng.distance_look(t, code, hist, map)
         return distance.Distance(words, self.params.N, t, code, hist=hi, d2=d2, delx=self.solution.delx)
 
@@ -213,8 +214,7 @@ class Solver:
         are fetched in this call unless ``hist=False``; nothing N x N leaves the device.  A field the host edited is
         pushed first, as solve_or_resume does.  Needs a field: prepare() first."""
         t = float(self.params.threshold if threshold is None else threshold)
-        eng = self._get_engine()
-        self._push_edited_U()
+        eng = self._look_engine()
         words, hi = eng.chords_look(t, hist)
         return chords.Chords(words, self.params.N, t, hist=hi, delx=self.solution.delx)
 

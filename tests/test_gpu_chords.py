@@ -311,3 +311,96 @@ def test_errors(gpu):
     co = chords.Chords(out, 128, 0.5, hist=hist[:8 * nb].reshape(2, 2, 2, nb))
     assert co.n('below') == int((bs.solvers[1]._engine.get_U() < 0.5).sum())
     bs.close(fetch_U=False)
+
+
+# ---------------------------------------------------------------------------
+# 7. the looks of one handle side by side (they share the scaffold of chs_look.h)
+# ---------------------------------------------------------------------------
+def _models(Ud, t):
+    """What the fetches behind a look at `Ud` below `t` hold, by the numpy models."""
+    from chsimpy_amd import components, distance
+    D2 = distance.squared_distance(Ud, t, 'below')
+    labels, table = components.label(Ud, t, 4, 'below')
+    return {'chords_hist': chords.chord_histograms(Ud, t), 'distance_hist': distance.histogram_of(D2), 'distance_map': D2,
+            'components_table': table, 'components_labels': labels}
+
+
+def _fetches(e):
+    return {k: getattr(e, k)() for k in ('chords_hist', 'distance_hist', 'distance_map', 'components_table', 'components_labels')}
+
+
+def _assert_fetches(got, want, what):
+    assert set(got) == set(want)
+    for k in want:
+        assert got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), (what, k)
+
+
+@pytest.mark.parametrize("N,dtype", [(65, 'float64'), (68, 'float32')])
+def test_the_five_looks_in_turn_do_not_disturb_each_other(gpu, N, dtype):
+    """N = 65 fp64: a row is one 64-bit word and a bit, no 16-byte rows; N = 68 fp32: 16-byte loads, a partial last word.
+    All five looks first, every fetch afterwards: each still holds its own look, equal to the numpy model."""
+    s = tgs.solver(N, 4, 'chirp', dtype)
+    s.prepare()
+    eng = s._engine
+    eng.set_U(mh.field_of(np.random.default_rng(N).random((N, N)) < 0.55))
+    Ud = eng.get_U()
+    assert eng.structure_factor().shape == (int(gpu.chs_structure_factor_bins(N)),)
+    mw = eng.morphology(T)
+    cw = eng.components(T, 4, _lib.CHS_CC_BELOW)
+    dw = eng.distance(T, _lib.CHS_CC_BELOW)
+    hw = eng.chords(T)
+    want = _models(Ud, T)
+    _assert_fetches(_fetches(eng), want, f"N={N} {dtype}")
+    from chsimpy_amd import components, distance
+    assert np.array_equal(cw, components.summary_of(want['components_table'], N))
+    assert np.array_equal(dw, distance.summary_of(want['distance_map']))
+    assert np.array_equal(hw, chords.summary_of(want['chords_hist']))
+    assert int(mw[1:6].sum()) + int(mw[0]) == (N + 1) ** 2 and 0 < int(dw[0]) == int((Ud < T).sum()) < N * N
+    for ms in (eng.morphology_ms(), eng.components_ms(), eng.distance_ms(), eng.chords_ms()):
+        assert ms >= 0.0
+    assert np.all(eng.structure_factor_ms() >= 0.0)
+    s.close(fetch_U=False)
+
+
+def test_a_rejected_look_leaves_the_last_one_in_place(gpu):
+    """A call with a threshold that is not finite is refused before anything of the last look is touched: morphology,
+    components, distance and chords alike go on answering for the look before it, its time included."""
+    N = 65
+    s = tgs.solver(N, 4, 'chirp')
+    s.prepare()
+    eng = s._engine
+    eng.set_U(mh.field_of(np.random.default_rng(5).random((N, N)) < 0.5))
+    eng.morphology(T), eng.components(T, 4, _lib.CHS_CC_BELOW), eng.distance(T, _lib.CHS_CC_BELOW), eng.chords(T)
+    before = _fetches(eng)
+    times = (eng.morphology_ms(), eng.components_ms(), eng.distance_ms(), eng.chords_ms())
+    assert min(times) >= 0.0
+    _assert_fetches(before, _models(eng.get_U(), T), 'the good looks')
+    o = _lib._i64ptr(np.zeros(32, dtype=np.int64))
+    for bad in (float('nan'), float('inf')):
+        for rc in (gpu.chs_morphology(eng._h, bad, o), gpu.chs_components(eng._h, bad, 4, 0, o),
+                   gpu.chs_distance(eng._h, bad, 0, o), gpu.chs_chords(eng._h, bad, o)):
+            assert rc == _lib.CHS_EINVAL and 'finite' in gpu.chs_last_error().decode()
+    assert gpu.chs_components(eng._h, float('nan'), 5, 0, o) == _lib.CHS_EINVAL      # doubly wrong: the threshold comes first
+    assert 'finite' in gpu.chs_last_error().decode()
+    assert gpu.chs_distance(eng._h, float('nan'), 2, o) == _lib.CHS_EINVAL
+    assert 'finite' in gpu.chs_last_error().decode()
+    _assert_fetches(_fetches(eng), before, 'after the rejected calls')
+    assert (eng.morphology_ms(), eng.components_ms(), eng.distance_ms(), eng.chords_ms()) == times
+    s.close(fetch_U=False)
+
+
+@pytest.mark.parametrize("order", [(0, 1), (1, 0)])
+def test_the_batch_buffers_hold_the_last_member_looked_at(gpu, order):
+    """B = 2 at N = 128: a batch has one buffer set per kind of look; after looks at both members what is fetched is the
+    second one's."""
+    bs = BatchSolver(tgs._members(128, 2, 10))
+    bs.prepare()
+    b = bs._batch
+    fields = [b.get_U(m) for m in range(2)]
+    ts = [float(np.median(U)) for U in fields]
+    assert not np.array_equal(fields[0] < ts[0], fields[1] < ts[1])
+    for m in order:
+        b.chords(m, ts[m]), b.distance(m, ts[m], _lib.CHS_CC_BELOW), b.components(m, ts[m], 4, _lib.CHS_CC_BELOW)
+    last = order[-1]
+    _assert_fetches(_fetches(b), _models(fields[last], ts[last]), f"member {last} after {order}")
+    bs.close(fetch_U=False)
