@@ -75,6 +75,62 @@ def reference(X):
     return D2, words, hist
 
 
+def isqrt_of(v):
+    """math.isqrt element by element for an int64 array of values below 2^52 (the float root is off by one at most)."""
+    v = np.asarray(v, dtype=np.int64)
+    k = np.floor(np.sqrt(v.astype(np.float64))).astype(np.int64)
+    k -= k * k > v
+    k += (k + 1) * (k + 1) <= v
+    return k
+
+
+def words_and_hist(D2):
+    """(words int64 [5], hist int64 [bins]) of a squared-distance map by plain counting, at any N."""
+    N = D2.shape[0]
+    flat = D2.ravel().astype(np.int64)
+    fin = flat[(flat > 0) & (flat < INF)]
+    words = np.array([int((flat > 0).sum()), 0, -1, 0, int((flat == INF).sum())], dtype=np.int64)
+    bins = math.isqrt(2 * (N - 1) ** 2) + 1
+    hist = np.zeros(bins, dtype=np.int64)
+    if fin.size:
+        words[1] = fin.max()
+        words[2] = int(np.flatnonzero(flat == fin.max())[0])
+        words[3] = fin.sum()
+        hist = np.bincount(isqrt_of(fin), minlength=bins).astype(np.int64)
+    return words, hist
+
+
+def reference_exact(X):
+    """`reference` at any N: (D2, words, hist) of the boolean foreground X from the INDICES of scipy's exact transform,
+    D2 = (i - ii)^2 + (j - jj)^2 in integers with (ii, jj) the nearest background pixel scipy names -- no rounded float
+    anywhere.  All foreground: CHS_DT_INF; all background: 0, as in `reference`."""
+    X = np.asarray(X, dtype=bool)
+    N = X.shape[0]
+    if X.all():
+        D2 = np.full((N, N), INF, dtype=np.int32)
+    elif not X.any():
+        D2 = np.zeros((N, N), dtype=np.int32)
+    else:
+        idx = ndimage.distance_transform_edt(X, return_distances=False, return_indices=True)
+        di = np.arange(N, dtype=np.int64)[:, None] - idx[0]
+        dj = np.arange(N, dtype=np.int64)[None, :] - idx[1]
+        assert not X[idx[0], idx[1]].any()               # (what scipy names is a background pixel)
+        D2 = (di * di + dj * dj).astype(np.int32)
+    words, hist = words_and_hist(D2)
+    assert words[0] == int(X.sum())
+    return D2, words, hist
+
+
+def closed_form(N, background):
+    """D2 int32 [N][N] of a grid that is foreground but for the pixels `background`: min_k (i-i_k)^2 + (j-j_k)^2."""
+    i = np.arange(N, dtype=np.int64)
+    D2 = None
+    for ik, jk in background:
+        d = ((i - ik) ** 2)[:, None] + ((i - jk) ** 2)[None, :]
+        D2 = d if D2 is None else np.minimum(D2, d)
+    return D2.astype(np.int32)
+
+
 def check_look(di, X, what=''):
     """A `Distance` (with histogram and map where fetched) against the reference of the boolean foreground X."""
     D2, words, hist = reference(X)
@@ -85,6 +141,17 @@ def check_look(di, X, what=''):
     if di.d2 is not None:
         assert di.d2.dtype == np.int32 and np.array_equal(di.d2, D2), (what, np.argwhere(di.d2 != D2)[:5])
     return words
+
+
+def check_against(di, ref, what=''):
+    """A `Distance` (with histogram and map where fetched) against a (D2, words, hist) computed once by the caller."""
+    D2, words, hist = ref
+    assert di.words.dtype == np.int64 and np.array_equal(di.words, words), (what, di.words, words)
+    if di.hist is not None:
+        assert di.hist.dtype == np.int64 and di.hist.shape == hist.shape, what
+        assert np.array_equal(di.hist, hist), (what, np.flatnonzero(di.hist != hist)[:5])
+    if di.d2 is not None:
+        assert di.d2.dtype == np.int32 and np.array_equal(di.d2, D2), (what, np.argwhere(di.d2 != D2)[:5])
 
 
 def model_look(U, t, side):
@@ -185,6 +252,56 @@ def test_model_against_brute_force(N, density):
     X = rng.random((N, N)) < density
     for Y in (X, ~X, np.ones((N, N), dtype=bool), np.zeros((N, N), dtype=bool)):
         assert np.array_equal(distance.squared_distance(mh.field_of(Y), T), brute_force(Y))
+
+
+def _assert_same_reference(a, b, what):
+    for x, y, k in zip(a, b, ('D2', 'words', 'hist')):
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), (what, k)
+
+
+@pytest.mark.parametrize("N", [8, 33, 65, 513])
+def test_reference_exact_equals_reference_up_to_513(N):
+    """The index-based reference against the rounded-float one where that is exact: the random densities of the tests
+    above, both sides, the two uniform grids, and the patterns of `patterns`."""
+    for density in (0.3, 0.6, 0.95, 0.995):
+        X = np.random.default_rng(1000 * N + int(1000 * density)).random((N, N)) < density
+        for Y in (X, ~X):
+            _assert_same_reference(reference_exact(Y), reference(Y), (N, density))
+    for Y in (np.ones((N, N), dtype=bool), np.zeros((N, N), dtype=bool)):
+        _assert_same_reference(reference_exact(Y), reference(Y), (N, 'uniform'))
+    if N <= 65:
+        for name, U, _ in patterns(N, tile_from_source()):
+            for Y in (U < T, ~(U < T)):
+                _assert_same_reference(reference_exact(Y), reference(Y), (N, name))
+
+
+def test_reference_exact_equals_the_model_above_513():
+    """N = 700, beyond `reference`: the index-based reference and the numpy model of the two passes give the same map,
+    words and histogram at a dense, a sparse and a nearly empty background."""
+    N = 700
+    for density in (0.6, 0.95, 0.999):
+        U = mh.field_of(np.random.default_rng(700 + int(1000 * density)).random((N, N)) < density)
+        D2 = distance.squared_distance(U, T)
+        ref = reference_exact(U < T)
+        assert np.array_equal(ref[0], D2), density
+        assert np.array_equal(ref[1], distance.summary_of(D2)) and np.array_equal(ref[2], distance.histogram_of(D2))
+        assert ref[1][1] >= 2 and ref[1][4] == 0
+
+
+@pytest.mark.parametrize("background", [((0, 0),), ((0, 0), (699, 3), (350, 699))], ids=['one-pixel', 'three-pixels'])
+def test_reference_exact_equals_the_closed_form(background):
+    """N = 700, a background of one pixel and of three: D2 = min_k (i - i_k)^2 + (j - j_k)^2."""
+    N = 700
+    X = np.ones((N, N), dtype=bool)
+    for i, j in background:
+        X[i, j] = False
+    D2 = closed_form(N, background)
+    ref = reference_exact(X)
+    assert np.array_equal(ref[0], D2)
+    assert np.array_equal(ref[1], distance.summary_of(D2)) and np.array_equal(ref[2], distance.histogram_of(D2))
+    if len(background) == 1:
+        assert ref[1].tolist() == [N * N - 1, 2 * (N - 1) ** 2, N * N - 1, 2 * N * sum(k * k for k in range(N)), 0]
+        assert ref[2][-1] >= 1 and len(ref[2]) == distance.bin_count(N)
 
 
 def test_the_sentinel_and_ninf_by_the_definition():

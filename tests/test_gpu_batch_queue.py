@@ -313,3 +313,22 @@ def test_experiment_queue_writes_the_results_of_the_member_path(gpu, tmp_path, c
     one, queue = open(tmp_path / 'one-results.csv', 'rb').read(), open(tmp_path / 'queue-results.csv', 'rb').read()
     assert len(one.splitlines()) == 13
     assert one == queue
+
+
+def test_experiment_queue_measurements_equal_the_member_path(gpu, tmp_path, capsys):
+    """The same ensemble with every measurement flag: `--batch 4 --queue` looks at its members behind the call, those that
+    stopped early and handed their seat on included, and writes the five files the member path writes, byte for byte;
+    -results.csv likewise."""
+    flags = [m.flag for m in ex.MEASUREMENTS]
+    assert flags == ['--domain-size', '--morphology', '--droplets', '--widths', '--chords']
+    base = ['-N', '128', '-R', '12', '-n', '3000', '-K', repr(KAPPA)] + flags
+    ex.main(base + ['--concurrent', '1', '--file-id', str(tmp_path / 'one')])
+    capsys.readouterr()
+    ex.main(base + ['--batch', '4', '--queue', '--file-id', str(tmp_path / 'queue')])
+    assert 'not taken' not in capsys.readouterr().out
+    for m in ex.MEASUREMENTS:
+        one = open(tmp_path / f'one-{m.suffix}.csv', 'rb').read()
+        assert len(one.splitlines()) == 13 and one.splitlines()[0].decode() == ','.join(m.cols), m.key
+        assert one == open(tmp_path / f'queue-{m.suffix}.csv', 'rb').read(), m.key
+    one = open(tmp_path / 'one-results.csv', 'rb').read()
+    assert len(one.splitlines()) == 13 and one == open(tmp_path / 'queue-results.csv', 'rb').read()

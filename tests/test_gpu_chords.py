@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import chsimpy_amd
-from chsimpy_amd import _lib, chords
+from chsimpy_amd import _lib, chords, experiment as ex
 from chsimpy_amd.batch import BatchSolver
 from gpu_helpers import make
 import test_gpu_spectrum as tgs
@@ -246,6 +246,50 @@ def test_batch_equals_the_single_solvers_and_leaves_the_members_alone(gpu, N, en
     for m in range(B):
         assert np.array_equal(looked[m][0], plain[m][0]) and np.array_equal(looked[m][1], plain[m][1]), m
         assert looked[m][2] == plain[m][2], m
+
+
+# ---------------------------------------------------------------------------
+# 5b. experiment
+# ---------------------------------------------------------------------------
+class ModelSolver:
+    """What experiment._chords_of asks of a Solver, answered by the numpy model on a field."""
+
+    def __init__(self, U, threshold):
+        self.U, self.threshold = U, threshold
+
+    def chords(self, hist=False):
+        return host.model_look(self.U, self.threshold)
+
+
+def test_experiment_chords_batch_equals_member_path(gpu, tmp_path, capsys):
+    """`-N 136 -R 4 -n 80 --chords` one by one and with `--batch 2` write identical -chords.csv, their -results.csv is
+    byte for byte that of a run without the flag, and without the flag no such file appears.  Every row is what
+    experiment._chords_of gives from the numpy model on the member's exported final field (the floats are written with
+    repr: the parsed values are compared exactly)."""
+    base = ['-N', '136', '-R', '4', '-n', '80']
+    ex.main(base + ['--concurrent', '1', '--file-id', str(tmp_path / 'plain')])
+    ex.main(base + ['--concurrent', '1', '--chords', '--export-csv', 'U', '--file-id', str(tmp_path / 'one')])
+    capsys.readouterr()
+    ex.main(base + ['--batch', '2', '--chords', '--file-id', str(tmp_path / 'batch')])
+    assert 'not taken' not in capsys.readouterr().out
+    one, batch = open(tmp_path / 'one-chords.csv').read(), open(tmp_path / 'batch-chords.csv').read()
+    assert one == batch
+    lines = one.splitlines()
+    assert lines[0] == ','.join(ex.CHORDS_COLS) and len(lines) == 5
+    ints = [c in ex.MEASUREMENTS[4].int_cols for c in ex.CHORDS_COLS]
+    assert ex.MEASUREMENTS[4].key == 'chords' and sum(ints) == 13
+    for i, ln in enumerate(lines[1:]):
+        f = ln.split(',')
+        got = [int(v) if k else float(v) for v, k in zip(f, ints)]
+        U = np.loadtxt(tmp_path / f'one-run{i}.solution.U.csv', delimiter=',')
+        assert U.shape == (136, 136) and got[0] == i and got[1] == chsimpy_amd.Parameters().threshold
+        want = (i,) + ex._chords_of(ModelSolver(U, got[1]))
+        assert len(got) == len(want) == 22
+        assert all(g == w or (g != g and w != w) for g, w in zip(got, want)), (i, got, want)
+        assert got[2] > 0 and got[17] > 0                                        # inner chords of both phases
+    assert not (tmp_path / 'plain-chords.csv').exists()
+    plain = open(tmp_path / 'plain-results.csv', 'rb').read()
+    assert plain == open(tmp_path / 'one-results.csv', 'rb').read() == open(tmp_path / 'batch-results.csv', 'rb').read()
 
 
 # ---------------------------------------------------------------------------

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import chsimpy_amd
-from chsimpy_amd import _lib, components, distance
+from chsimpy_amd import _lib, components, distance, experiment as ex
 from chsimpy_amd.batch import BatchSolver
 from gpu_helpers import make
 import test_gpu_spectrum as tgs
@@ -228,6 +228,55 @@ def test_batch_equals_the_single_solvers_and_leaves_the_members_alone(gpu, N, en
     for m in range(B):
         assert np.array_equal(looked[m][0], plain[m][0]) and np.array_equal(looked[m][1], plain[m][1]), m
         assert looked[m][2] == plain[m][2], m
+
+
+# ---------------------------------------------------------------------------
+# 5b. experiment
+# ---------------------------------------------------------------------------
+def same_values(got, want):
+    """Parsed csv values against computed ones: equal, or NaN on both sides."""
+    return len(got) == len(want) and all(g == w or (g != g and w != w) for g, w in zip(got, want))
+
+
+class ModelSolver:
+    """What experiment._widths_of asks of a Solver, answered by the numpy model on a field."""
+
+    def __init__(self, U, threshold):
+        self.U, self.threshold = U, threshold
+
+    def distance(self, side='below'):
+        return host.model_look(self.U, self.threshold, side)
+
+
+def test_experiment_widths_batch_equals_member_path(gpu, tmp_path, capsys):
+    """`-N 136 -R 4 -n 80 --widths` one by one and with `--batch 2` write identical -widths.csv, their -results.csv is
+    byte for byte that of a run without the flag, and without the flag no such file appears.  Every row is what
+    experiment._widths_of gives from the numpy model on the member's exported final field (the floats are written with
+    repr: the parsed values are compared exactly)."""
+    base = ['-N', '136', '-R', '4', '-n', '80']
+    ex.main(base + ['--concurrent', '1', '--file-id', str(tmp_path / 'plain')])
+    ex.main(base + ['--concurrent', '1', '--widths', '--export-csv', 'U', '--file-id', str(tmp_path / 'one')])
+    capsys.readouterr()
+    ex.main(base + ['--batch', '2', '--widths', '--file-id', str(tmp_path / 'batch')])
+    assert 'not taken' not in capsys.readouterr().out
+    one, batch = open(tmp_path / 'one-widths.csv').read(), open(tmp_path / 'batch-widths.csv').read()
+    assert one == batch
+    lines = one.splitlines()
+    assert lines[0] == ','.join(ex.WIDTHS_COLS) and len(lines) == 5
+    ints = [c in ex.MEASUREMENTS[3].int_cols for c in ex.WIDTHS_COLS]
+    assert ex.MEASUREMENTS[3].key == 'widths' and sum(ints) == 7
+    for i, ln in enumerate(lines[1:]):
+        f = ln.split(',')
+        assert all(('.' not in v and 'e' not in v) == k or v == 'nan' for v, k in zip(f, ints)), ln
+        got = [int(v) if k else float(v) for v, k in zip(f, ints)]
+        U = np.loadtxt(tmp_path / f'one-run{i}.solution.U.csv', delimiter=',')
+        assert U.shape == (136, 136) and got[0] == i and got[1] == chsimpy_amd.Parameters().threshold
+        want = (i,) + ex._widths_of(ModelSolver(U, got[1]))
+        assert same_values(got, want), (i, got, want)
+        assert got[2] + got[8] == 136 * 136 and 0 < got[2] < 136 * 136 and got[3] >= 1.0      # both sides are there
+    assert not (tmp_path / 'plain-widths.csv').exists()
+    plain = open(tmp_path / 'plain-results.csv', 'rb').read()
+    assert plain == open(tmp_path / 'one-results.csv', 'rb').read() == open(tmp_path / 'batch-results.csv', 'rb').read()
 
 
 # ---------------------------------------------------------------------------
