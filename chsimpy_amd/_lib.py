@@ -28,6 +28,10 @@ CHS_CC_BELOW, CHS_CC_ABOVE = 0, 1
 CHS_DT_WORDS = 5              # int64 words of chs_distance: fg, d2max, d2max_first, sumd2, ninf
 CHS_DT_INF = 1 << 30          # D2 of every pixel of a grid without background
 CHS_CH_WORDS = 24             # int64 words of chs_chords: six per (phase, direction)
+CHS_CMP_IWORDS = 7            # int64 words of chs_composition: n_total, n_nan, n_inf, n_below, n_under, n_over, nbins
+CHS_CMP_FWORDS = 11           # its float64 words: min, max, sum, sum_below, center, m2, m3, m4, lo, hi, scale
+CHS_CMP_MAX_BINS = 4096
+CHS_CMP_MAX_RANKS = 8         # ranks of one chs_composition_select
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -51,6 +55,8 @@ SYMBOLS = (
     'chs_batch_distance', 'chs_batch_distance_hist', 'chs_batch_distance_map',
     'chs_chords_bins', 'chs_chords', 'chs_chords_hist', 'chs_chords_last_ms', 'chs_chords_tile',
     'chs_batch_chords', 'chs_batch_chords_hist',
+    'chs_composition', 'chs_composition_hist', 'chs_composition_select', 'chs_composition_last_ms', 'chs_composition_tile',
+    'chs_batch_composition', 'chs_batch_composition_hist', 'chs_batch_composition_select', 'chs_batch_composition_last_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -201,6 +207,15 @@ def load():
     lib.chs_chords_tile.argtypes = [i32p, i32p, i32p]
     lib.chs_batch_chords.argtypes = [vp, C.c_int32, C.c_double, i64p]
     lib.chs_batch_chords_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_composition.argtypes = [vp, C.c_double, C.c_int32, C.c_double, C.c_double, i64p, dp]
+    lib.chs_composition_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_composition_select.argtypes = [vp, C.c_int32, i64p, dp]
+    lib.chs_composition_last_ms.argtypes = [vp, dp]
+    lib.chs_composition_tile.argtypes = [i32p, i32p, i32p, i32p]
+    lib.chs_batch_composition.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, i64p, dp]
+    lib.chs_batch_composition_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_batch_composition_select.argtypes = [vp, C.c_int32, C.c_int32, i64p, dp]
+    lib.chs_batch_composition_last_ms.argtypes = [vp, dp]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -269,6 +284,26 @@ def chords_bins(N):
     return int(load().chs_chords_bins(int(N)))
 
 
+def composition_tile():
+    """(elems_per_thread, threads, max_groups, digit_bits) of the kernels of chs_composition (chs_composition_tile): a
+    workgroup of `threads` threads takes tiles of threads * elems_per_thread elements, every max_groups-th one where the
+    field has more tiles; the digits of the radix select have digit_bits bits."""
+    v = [C.c_int32(0) for _ in range(4)]
+    rc = load().chs_composition_tile(*(C.byref(x) for x in v))
+    if rc != CHS_OK:
+        raise EngineError(f"chs_composition_tile failed ({rc})")
+    return tuple(int(x.value) for x in v)
+
+
+def composition_sum_terms(N, tile=None):
+    """(E, D) of the error bound of the float sums of chs_composition at grid size N: the elements
+    a thread adds one after the other, and the depth of the trees above it."""
+    ept, threads, max_groups, _ = tile or composition_tile()
+    tiles = -(-(N * N) // (threads * ept))
+    groups = min(tiles, max_groups)
+    return ept * -(-tiles // groups), (threads - 1).bit_length() + (max_groups - 1).bit_length()
+
+
 def __getattr__(name):
     if name == 'CC_TILE':   # read from the library at the first use: importing the binding does not load it
         return components_tile()
@@ -301,9 +336,17 @@ class _Looks:
     but for the prefix of the symbol (`_prefix`: ``chs_`` or ``chs_batch_``) and what stands in front of the threshold
     (`lead`: nothing, or the member).  A batch has one set of buffers, so what is fetched is that of its last look."""
 
+    _cmp_nbins = 0
+
     def _look_call(self, name, *args):
         what = self._prefix + name
         self._check(getattr(self.lib, what)(self._h, *args), what)
+
+    def _last_ms(self, symbol):
+        """Device time (ms) of the last look of a kind, by the symbol that answers it."""
+        ms = C.c_double(0.0)
+        self._check(getattr(self.lib, symbol)(self._h, C.byref(ms)), symbol)
+        return float(ms.value)
 
     def _components(self, lead, threshold, connectivity, side):
         out = np.empty(CHS_CC_WORDS, dtype=np.int64)
@@ -363,6 +406,32 @@ class _Looks:
     def _chords_look(self, lead, threshold, hist):
         words = self._chords(lead, threshold)
         return words, (self.chords_hist() if hist else None)
+
+    def _composition(self, lead, threshold, nbins, lo, hi):
+        iw, fw = np.empty(CHS_CMP_IWORDS, dtype=np.int64), np.empty(CHS_CMP_FWORDS, dtype=np.float64)
+        self._look_call('composition', *lead, float(threshold), int(nbins), float(lo), float(hi), _i64ptr(iw), _dptr(fw))
+        self._cmp_nbins = int(nbins)
+        return iw, fw
+
+    def composition_hist(self, nbins=None):
+        """int64 [nbins] of the last look: the pixels by bin (nbins: that of the last look of this object)."""
+        out = np.empty(self._cmp_nbins if nbins is None else int(nbins), dtype=np.int64)
+        self._look_call('composition_hist', len(out), _i64ptr(out))
+        return out
+
+    def _composition_look(self, lead, threshold, nbins, lo, hi, hist):
+        iw, fw = self._composition(lead, threshold, nbins, lo, hi)
+        return iw, fw, (self.composition_hist() if hist else None)
+
+    def _composition_select(self, lead, ranks):
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        out = np.empty(ranks.size, dtype=np.float64)
+        self._look_call('composition_select', *lead, int(ranks.size), _i64ptr(ranks), _dptr(out))
+        return out
+
+    def composition_ms(self):
+        """Device time (ms) of the last `composition` or `composition_select`."""
+        return self._last_ms(self._prefix + 'composition_last_ms')
 
 
 class Engine(_Looks):
@@ -517,11 +586,20 @@ class Engine(_Looks):
         """One look with what belongs to it: (words, histograms or None)."""
         return self._chords_look((), threshold, hist)
 
-    def _last_ms(self, symbol):
-        """Device time (ms) of the last look of a kind, by the symbol that answers it."""
-        ms = C.c_double(0.0)
-        self._check(getattr(self.lib, symbol)(self._h, C.byref(ms)), symbol)
-        return float(ms.value)
+    def composition(self, threshold, nbins=15, lo=float('nan'), hi=float('nan')):
+        """The int64 and the float64 words of the composition of the field the device holds (chs_composition;
+        chsimpy_amd/composition.py names them); lo and hi both NaN: the field's own range.  The histogram of this look:
+        `composition_hist`."""
+        return self._composition((), threshold, nbins, lo, hi)
+
+    def composition_look(self, threshold, nbins=15, lo=float('nan'), hi=float('nan'), hist=True):
+        """One look with what belongs to it: (integer words, float words, histogram or None)."""
+        return self._composition_look((), threshold, nbins, lo, hi, hist)
+
+    def composition_select(self, ranks):
+        """The ranks[k]-th smallest pixels (0-based, at most CHS_CMP_MAX_RANKS of them), exactly
+        (chs_composition_select)."""
+        return self._composition_select((), ranks)
 
     def morphology_ms(self):
         """Device time (ms) of the last `morphology`."""
@@ -694,6 +772,17 @@ class Batch(_Looks):
 
     def chords_look(self, member, threshold, hist=True):
         return self._chords_look((int(member),), threshold, hist)
+
+    def composition(self, member, threshold, nbins=15, lo=float('nan'), hi=float('nan')):
+        """`Engine.composition` of one member (chs_batch_composition)."""
+        return self._composition((int(member),), threshold, nbins, lo, hi)
+
+    def composition_look(self, member, threshold, nbins=15, lo=float('nan'), hi=float('nan'), hist=True):
+        return self._composition_look((int(member),), threshold, nbins, lo, hi, hist)
+
+    def composition_select(self, member, ranks):
+        """`Engine.composition_select` of one member (chs_batch_composition_select)."""
+        return self._composition_select((int(member),), ranks)
 
     def get_state(self, member):
         s = chs_state()

@@ -126,7 +126,8 @@ class _Member:
     def morphology(self, threshold):
         return self._b.morphology(threshold, self._m)
 
-    _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look')
+    _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
+              'composition_look', 'composition_select')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -308,6 +309,10 @@ class BatchSolver:
     def chords(self, member=None, threshold=None, hist=True):
         """The members' chord lengths (`Solver.chords`), a `chords.Chords` each: _member_by_member."""
         return self._member_by_member('chords', member, threshold, hist)
+
+    def composition(self, member=None, threshold=None, bins=15, range=None, quantiles=(0.05, 0.5, 0.95), hist=True):
+        """The members' compositions (`Solver.composition`), a `composition.Composition` each: _member_by_member."""
+        return self._member_by_member('composition', member, threshold, bins, range, quantiles, hist)
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

@@ -165,6 +165,7 @@ struct Batch {
   void* cc = nullptr;            // chs_batch_components: the batch's one set of buffers (chs_components.hip), at the first look
   void* dt = nullptr;            // chs_batch_distance: the batch's one set of buffers (chs_distance.hip), at the first look
   void* ch = nullptr;            // chs_batch_chords: the batch's one set of buffers (chs_chords.hip), at the first look
+  void* cmp = nullptr;           // chs_batch_composition: the batch's one set of buffers (chs_composition.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -185,6 +186,7 @@ void batch_free(Batch* b) {
   chs_cc_free(&b->cc);
   chs_dt_free(&b->dt);
   chs_ch_free(&b->ch);
+  chs_cmp_free(&b->cmp);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -858,4 +860,31 @@ extern "C" int chs_batch_chords_hist(chs_batch h, int32_t nbins, int64_t* out) {
   Batch* b = as_batch(h);
   if (!b) return bad("chs_batch_chords_hist: null handle");
   return chs_ch_hist(b->ch, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_chords_hist");
+}
+
+// The composition of one member: the single handle's looks on the batch's stream, with the batch's one set of buffers.
+extern "C" int chs_batch_composition(chs_batch h, int32_t member, double threshold, int32_t nbins, double lo, double hi,
+                                     int64_t* iw, double* fw) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_composition: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_composition: no such member");
+  return chs_cmp_look(b->m[(size_t)member], b->stream, &b->cmp, threshold, nbins, lo, hi, iw, fw, "chs_batch_composition");
+}
+
+extern "C" int chs_batch_composition_hist(chs_batch h, int32_t nbins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_composition_hist: null handle");
+  return chs_cmp_hist(b->cmp, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_composition_hist");
+}
+
+extern "C" int chs_batch_composition_select(chs_batch h, int32_t member, int32_t nq, const int64_t* ranks, double* values) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_composition_select: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_composition_select: no such member");
+  return chs_cmp_select(b->m[(size_t)member], b->stream, &b->cmp, nq, ranks, values, "chs_batch_composition_select");
+}
+
+extern "C" int chs_batch_composition_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_cmp_last_ms(b, b ? b->cmp : nullptr, ms, "chs_batch_composition");
 }

@@ -253,6 +253,7 @@ struct Engine {
   void* cc = nullptr;          // connected components: labels, numbers, table, result, events (chs_components.hip), at the first look
   void* dt = nullptr;          // distance transform: band masks, carries, D2, histogram, result, events (chs_distance.hip), at the first look
   void* ch = nullptr;          // chord lengths: bit planes, histograms, result, events (chs_chords.hip), at the first look
+  void* cmp = nullptr;         // composition: partial slots, histogram, select tables, result, events (chs_composition.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -441,3 +442,16 @@ int chs_ch_look(Engine* E, hipStream_t s, void** buf, double threshold, int64_t*
 int chs_ch_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
 void chs_ch_free(void** buf);
 void chs_ch_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- composition (chs_composition.hip) ----------------------------------------
+// Range, sums, histogram and central moments of the values of E's field on stream `s` with the
+// buffer set *buf (the handle's own, or the batch's one set), allocated here at the first look: iw[CHS_CMP_IWORDS],
+// fw[CHS_CMP_FWORDS].  The histogram of the last look of a buffer set: chs_cmp_hist.  chs_cmp_select: exact order
+// statistics, a look of its own with the same buffer set; it leaves the histogram alone.
+int chs_cmp_look(Engine* E, hipStream_t s, void** buf, double threshold, int32_t nbins, double lo, double hi, int64_t* iw,
+                 double* fw, const char* who);
+int chs_cmp_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
+int chs_cmp_select(Engine* E, hipStream_t s, void** buf, int32_t nq, const int64_t* ranks, double* values, const char* who);
+int chs_cmp_last_ms(const void* h, const void* buf, double* ms, const char* what);
+void chs_cmp_free(void** buf);
+void chs_cmp_forget(void* buf);   // the buffers stay, the last look goes

@@ -1,5 +1,6 @@
 // chs_look.h -- what the looks at the field have in common (chs_spectrum, chs_morphology, chs_components, chs_distance,
-// chs_chords .hip): how a kernel loads the field, and the host side's bracket around a look.
+// chs_chords, chs_composition .hip): how a kernel loads the field, and the host side's bracket
+// around a look.
 // Only what is textually the same in those files is here; what a look allocates, launches and checks is its own.
 #pragma once
 #include <cmath>

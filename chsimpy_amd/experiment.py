@@ -177,6 +177,16 @@ def _chords_of(solver):
     return row
 
 
+def _composition_of(solver):
+    """(threshold, n_nan, min, max, mean, var, SA, mean_below, mean_above, q05, q50, q95) of a member's final field: one
+    look behind its run and one select, without the histogram; NaN where a value does not exist."""
+    nan = float('nan')
+    co = solver.composition(bins=1, quantiles=(0.05, 0.5, 0.95), hist=False)
+    val = lambda v: nan if v is None else v
+    return (co.threshold, co.n_nan, co.min, co.max, val(co.mean), val(co.var), co.SA, val(co.mean_below), val(co.mean_above),
+            co.quantiles.get(0.05, nan), co.quantiles.get(0.5, nan), co.quantiles.get(0.95, nan))
+
+
 DOMAINS_COLS = ('id', 'k1', 'ell', 'ell_phys')
 MORPHOLOGY_COLS = ('id', 'threshold', 'n_A', 'SA', 'perimeter', 'perimeter_inner', 'euler8', 'euler4')
 DROPLETS_COLS = ('id', 'threshold', 'connectivity', 'count_below', 'largest_below', 'spanning_below', 'mean_area_below',
@@ -185,6 +195,8 @@ WIDTHS_COLS = ('id', 'threshold') + tuple(f"{k}_{side}" for side in ('below', 'a
                                           for k in ('fg', 'r_max', 'r2_mean', 'r_floor_mean', 'q50', 'q90'))
 CHORDS_COLS = ('id', 'threshold') + tuple(f"{k}_{phase}_{d}" for phase in ('below', 'above') for d in ('rows', 'cols')
                                           for k in ('count', 'mean', 'mean_weighted', 'max', 'cut'))
+COMPOSITION_COLS = ('id', 'threshold', 'n_nan', 'min', 'max', 'mean', 'var', 'SA', 'mean_below', 'mean_above', 'q05', 'q50',
+                    'q95')
 
 
 # `--dry-run`: rows made up from the run id, as the members' records are (_dry_member) -- members without device work
@@ -213,6 +225,11 @@ def _dry_chords(i, p, opts):
     """i + 1 inner chords of 2 and 4 pixels below along the rows, ..."""
     return (float(p.threshold), i + 1, 3.0, 10.0 / 3.0, 4, 1, i + 2, 1.5, 1.75, 2, 0,
             i + 3, float(i + 2), i + 2.5, 2 * i + 4, p.N, i + 4, 0.1 * (i + 1), 1.0 / (i + 3), i + 5, p.N + 1)
+
+
+def _dry_composition(i, p, opts):
+    """i NaN pixels in a field of two compositions."""
+    return (float(p.threshold), i, 0.125, 0.875 + 0.001 * i, 0.5, 0.1 / (i + 1), 0.5, 0.25, 0.75, 0.126, 0.5, 0.874)
 
 
 class Measurement(NamedTuple):
@@ -267,27 +284,41 @@ MEASUREMENTS = (
                 lambda s, opts: _chords_of(s), _dry_chords),
 )
 
+# The looks at the values of the field rather than at its thresholded image: entries of the same kind, walked behind
+# MEASUREMENTS everywhere (ALL_MEASUREMENTS).  A tuple of its own only because tests/test_measurements_host.py pins
+# MEASUREMENTS to its five keys.
+FIELD_MEASUREMENTS = (
+    Measurement('composition', '--composition', 'measure the composition of every member\'s final field on the device '
+                'behind its run (range, moments, the means on either side of the threshold, exact quantiles): '
+                '<id>-composition.csv with id, threshold, n_nan, min, max, mean, var, SA, mean_below, mean_above, q05, q50, '
+                'q95',
+                'composition', COMPOSITION_COLS, frozenset({'id', 'n_nan'}),
+                lambda s, opts: _composition_of(s), _dry_composition),
+)
+ALL_MEASUREMENTS = MEASUREMENTS + FIELD_MEASUREMENTS
 
-def _asked(domains, morphology, droplets, widths, chords):
-    """The measurements a caller asked for, keyed like MEASUREMENTS: the dicts its rows go to."""
-    given = dict(domains=domains, morphology=morphology, droplets=droplets, widths=widths, chords=chords)
+
+def _asked(domains, morphology, droplets, widths, chords, composition=None):
+    """The measurements a caller asked for, keyed like ALL_MEASUREMENTS: the dicts its rows go to."""
+    given = dict(domains=domains, morphology=morphology, droplets=droplets, widths=widths, chords=chords,
+                 composition=composition)
     return {k: v for k, v in given.items() if v is not None}
 
 
 def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, postprocess=True, domains=None,
-                       morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None):
+                       morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None, composition=None):
     """One ensemble member on this rank's GPU; the 12-tuple of experiment.py:114-126.  ``domains``, ``morphology``,
-    ``droplets``, ``widths``, ``chords`` (a dict each): the member's row of that entry of MEASUREMENTS, measured on the
+    ``droplets``, ``widths``, ``chords``, ``composition`` (a dict each): the member's row of that entry of ALL_MEASUREMENTS, measured on the
     device behind its run at ``params.threshold``, goes to ``<dict>[run_id]`` (``droplets_connectivity`` 4 or 8: that of
     the droplets)."""
     from .simulator import Simulator
-    asked = _asked(domains, morphology, droplets, widths, chords)
+    asked = _asked(domains, morphology, droplets, widths, chords, composition)
     opts = {'droplets_connectivity': droplets_connectivity}
     params, fac_A0, fac_A1 = run_params(init_params, run_id, rand_values, A_list)
     simulator = Simulator(params, U_init)
     try:
         solution = simulator.solve()
-        for m in MEASUREMENTS:
+        for m in ALL_MEASUREMENTS:
             if m.key in asked:
                 asked[m.key][run_id] = m.row_of(simulator.solver, opts)
         simulator.export()
@@ -299,7 +330,7 @@ def run_experiment_gpu(run_id, init_params, rand_values, A_list, U_init=None, po
 
 
 def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postprocess=True, seats=None, domains=None,
-                  morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None):
+                  morphology=None, droplets=None, droplets_connectivity=4, widths=None, chords=None, composition=None):
     """Several ensemble members advanced together as one device workload (chsimpy_amd.batch.BatchSolver): what
     run_experiment_gpu does for each of them -- one solve_or_resume(ntmax), the export, the 12-tuple.  ``seats``: the
     members run as a seat queue, that many at a time (None: all of them from the first step on).  The measurements: as
@@ -307,14 +338,14 @@ def run_batch_gpu(run_ids, init_params, rand_values, A_list, U_init=None, postpr
     member on the batch's stream."""
     from .batch import BatchSolver
     from .simulator import Simulator
-    asked = _asked(domains, morphology, droplets, widths, chords)
+    asked = _asked(domains, morphology, droplets, widths, chords, composition)
     opts = {'droplets_connectivity': droplets_connectivity}
     runs = [run_params(init_params, i, rand_values, A_list) for i in run_ids]
     bs = BatchSolver([r[0] for r in runs], U_init, seats=seats)
     try:
         bs.prepare()
         solutions = bs.solve_or_resume()
-        for m in MEASUREMENTS:
+        for m in ALL_MEASUREMENTS:
             if m.key in asked:
                 rows = m.rows_of_batch(bs) if m.rows_of_batch else (m.row_of(s, opts) for s in bs.solvers)
                 asked[m.key].update(zip(run_ids, rows))
@@ -385,6 +416,7 @@ def _writer(measurement):
 
 # the writers by the names callers know: write_widths(file_id, rows) is write_rows with the widths entry
 write_domains, write_morphology, write_droplets, write_widths, write_chords = (_writer(m) for m in MEASUREMENTS)
+write_composition, = (_writer(m) for m in FIELD_MEASUREMENTS)
 
 
 def write_metadata(file_id, ep, extra=()):
@@ -412,7 +444,7 @@ def write_results(file_id, records):
 
 def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, world=1, device='cpu',
                  concurrent=1, batch=0, batch_fn=None, queue=False, queue_members=256, domains=None, morphology=None,
-                 droplets=None, droplets_connectivity=4, widths=None, chords=None):
+                 droplets=None, droplets_connectivity=4, widths=None, chords=None, composition=None):
     """Deal the runs to the ranks, execute, gather.  ``run_fn(run_id, init_params, rand_values,
     A_list)`` defaults to the GPU run; the CPU tests inject a stand-in.
 
@@ -432,14 +464,14 @@ def run_ensemble(init_params, ep, run_fn=None, U_init=None, dist=None, rank=0, w
     into queues of at most ``queue_members``; ``batch_fn`` is called once per queue.  A chirp batch has no queue:
     ``queue`` at such an N runs member by member, with the note.
 
-    ``domains``, ``morphology``, ``droplets``, ``widths``, ``chords`` (a dict each, with the default run functions): that
-    entry of MEASUREMENTS -- the domain size from the radially averaged structure factor (chsimpy_amd/spectrum.py), the
+    ``domains``, ``morphology``, ``droplets``, ``widths``, ``chords``, ``composition`` (a dict each, with the default run
+    functions): that entry of ALL_MEASUREMENTS -- the domain size from the radially averaged structure factor (chsimpy_amd/spectrum.py), the
     morphology (morphology.py), the connected components on both sides of the threshold at ``droplets_connectivity``
     (components.py), the distance transform on both sides (distance.py), the chord lengths of both phases along rows
-    and columns (chords.py) -- is measured on every member's final field, on the device behind its run at its
+    and columns (chords.py), the composition (composition.py) -- is measured on every member's final field, on the device behind its run at its
     ``params.threshold``, and left in ``<dict>[run_id]`` for this rank's runs (gather_rows)."""
     rand_values, A_list, nr_items = make_rand_values(ep)
-    dom = _asked(domains, morphology, droplets, widths, chords)   # (the run functions are called as ever without them)
+    dom = _asked(domains, morphology, droplets, widths, chords, composition)   # (the run functions are called as ever without them)
     if droplets is not None:
         dom['droplets_connectivity'] = int(droplets_connectivity)
     if run_fn is None:
@@ -531,7 +563,7 @@ def arg_parser():
                     'a member that stops hands its seat to the next one on the device')
     ap.add_argument('--queue-members', type=int, default=256, help='members of one queue at the most (each owns its device '
                     'arrays from the start)')
-    for m in MEASUREMENTS:
+    for m in ALL_MEASUREMENTS:
         ap.add_argument(m.flag, dest=m.key, action='store_true', help=m.help)
     ap.add_argument('--droplets-connectivity', type=int, choices=(4, 8), default=4, help='the connectivity of --droplets')
     ap.add_argument('--gpus', type=int, default=1, help='start this many ranks (one per GPU) from here when no launcher '
@@ -588,7 +620,7 @@ def main(argv=None):
                        + ([f"batch_per_rank, {a.batch}"] if a.batch > 0 else [])
                        + ([f"queue_members, {a.queue_members}"] if (a.batch > 0 and a.queue) else [])
                        + (["dry_run, True"] if a.dry_run else []))
-    asked = [m for m in MEASUREMENTS if getattr(a, m.key)]
+    asked = [m for m in ALL_MEASUREMENTS if getattr(a, m.key)]
     local = {m.key: {} for m in asked}
     opts = {'droplets_connectivity': a.droplets_connectivity}
     records = run_ensemble(p, ep, run_fn=_dry_member if a.dry_run else None, U_init=U_init, dist=dist, rank=rank,

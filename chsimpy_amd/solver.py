@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, distance, morphology, mport, spectrum
+from . import _lib, chords, components, composition, distance, morphology, mport, spectrum
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -217,6 +217,32 @@ class Solver:
         eng = self._look_engine()
         words, hi = eng.chords_look(t, hist)
         return chords.Chords(words, self.params.N, t, hist=hi, delx=self.solution.delx)
+
+    def composition(self, threshold=None, bins=15, range=None, quantiles=(0.05, 0.5, 0.95), hist=True):
+        """The values of the field the device holds: how far the two phases have moved towards their compositions, how
+        much material sits between them, and whether the field has left [0, 1] or gone NaN -- minimum, maximum, mean,
+        variance, skewness and kurtosis, the mean on either side of `threshold` (None: ``params.threshold``), a
+        histogram of ``bins`` bins over ``range`` (None: the field's own minimum and maximum; ``bins=15, range=None`` is
+        the reference's ``Uhist``) and the exact ``quantiles`` -- a self-contained `composition.Composition` from two
+        sweeps on the device between two calls, and one radix select for up to eight quantiles, which the run does not
+        notice; nothing N x N leaves the device.  A quantile q is the pixel of rank ``floor(q (n - n_nan - 1))`` among
+        those that are not NaN (``numpy.quantile(..., method='lower')``).  The histogram is fetched in this call unless
+        ``hist=False``.  A field the host edited is pushed first, as solve_or_resume does.  Needs a field: prepare()
+        first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        nbins = composition.check_bins(bins)
+        lo, hi = composition.check_range(range)
+        qs = [float(q) for q in (quantiles or ())]
+        eng = self._look_engine()
+        iw, fw, counts = eng.composition_look(t, nbins, lo, hi, hist)
+        sortable = int(iw[composition.CHS_CMP_N_TOTAL] - iw[composition.CHS_CMP_N_NAN])
+        found = {}
+        if sortable > 0:
+            ranks = [composition.quantile_rank(q, sortable) for q in qs]
+            for k in np.arange(0, len(ranks), composition.CHS_CMP_MAX_RANKS):   # (`range` is the argument)
+                part = slice(int(k), int(k) + composition.CHS_CMP_MAX_RANKS)
+                found.update(zip(qs[part], (float(v) for v in eng.composition_select(ranks[part]))))
+        return composition.Composition(iw, fw, self.params.N, t, hist=counts, quantiles=found, delx=self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

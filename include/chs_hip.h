@@ -420,6 +420,74 @@ int chs_chords_last_ms(chs_handle h, double* ms);
  * workgroup of the walk, and the lengths below which a chord goes to the workgroup's histogram. */
 int chs_chords_tile(int32_t* word_bits, int32_t* lines_per_group, int32_t* local_bins);
 
+/* ---- Composition: the values of the field themselves -- range, sums, histogram, central moments, exact order
+ * statistics ----
+ * Every value is the element widened to double first, for fp32 handles too.  A pixel is NaN, infinite or finite.
+ * chs_composition, for a finite threshold t, 1 <= nbins <= CHS_CMP_MAX_BINS and a range [lo, hi] (both finite with
+ * lo <= hi, or both NaN: the field's own MIN and MAX), in two sweeps over the field without a host round trip between:
+ *   iw: N_TOTAL = N^2; N_NAN; N_INF, the pixels that are +inf or -inf; N_BELOW, the pixels with x < t (the foreground of
+ *       chs_components with CHS_CC_BELOW: a NaN and x == t are not below, -inf is); N_UNDER, the pixels with x < lo, -inf
+ *       among them; N_OVER, those with x > hi, +inf among them; NBINS as given.
+ *   fw: MIN and MAX over the finite pixels (the infinite ones are counted by N_INF and would leave no range to bin);
+ *       SUM and SUM_BELOW, the sums of x over the finite pixels and over the finite pixels below t; CENTER = SUM /
+ *       (N_TOTAL - N_NAN - N_INF), brought into [MIN, MAX] where rounding left it an ulp outside; M2, M3, M4, the sums of (x - CENTER)^p over the finite pixels, not divided; LO, HI and
+ *       SCALE = nbins / (HI - LO) in double, 0 unless HI > LO: the numbers the bins were formed with.
+ *   the histogram, int64 [nbins]: a finite x with LO <= x <= HI is in bin min(nbins - 1, (int64)((x - LO) * SCALE)), a
+ *       subtraction and a multiplication in double (a product that is not below nbins, a NaN product included, is
+ *       bin nbins - 1).  A NaN pixel goes nowhere: sum(hist) + N_UNDER + N_OVER + N_NAN = N^2.
+ * A field without a finite pixel is no error: MIN = MAX = CENTER = LO = HI = NaN (with the field's own range), SCALE = 0,
+ * an empty histogram.
+ * The float sums are bit for bit the same from look to look: every thread adds a fixed number of elements in a fixed
+ * order, every workgroup stores its partial sums into a slot of its own and one workgroup reduces the slots by a fixed
+ * tree; no float atomics.  Their error bound: DESIGN.md section 3h; chs_composition_tile gives its operands.
+ * chs_composition_select: values[k] = the ranks[k]-th smallest pixel (0-based, ranks in [0, N^2), any order, repeats
+ * allowed), exactly, in the order of np.sort: a NaN of either sign sorts last and comes back as a NaN; -0.0 and +0.0 are
+ * neighbours and may come back as either.  1 <= nq <= CHS_CMP_MAX_RANKS.  A look of its own: it needs no chs_composition
+ * before it and leaves the histogram of the last one where it is; chs_composition_last_ms reports the later of the two.
+ * Both work on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: they read the field
+ * alone and write buffers of their own (allocated at the first look, freed with the handle), so the run does not notice
+ * them.  The histogram of the last chs_composition stays available until the next one.  The looks check themselves (the
+ * pixels add up as above, N_BELOW <= N^2, MIN <= SUM / n <= MAX within the error bound of SUM, and for every selected rank r the keys below the one
+ * found are at most r and r is below that count plus the count of keys equal to it): a violation is CHS_ECHECK and
+ * chs_last_error names it.  CHS_EINVAL, the last look undisturbed: a null argument, a threshold that is not finite,
+ * nbins outside [1, CHS_CMP_MAX_BINS], exactly one of lo and hi NaN, lo > hi, an infinite bound, nq outside
+ * [1, CHS_CMP_MAX_RANKS], a rank outside [0, N^2), a fetch with another nbins than the look's.  CHS_ESTATE for _hist
+ * without a chs_composition, for _last_ms without either. */
+#define CHS_CMP_MAX_BINS 4096
+#define CHS_CMP_MAX_RANKS 8
+#define CHS_CMP_IWORDS 7
+#define CHS_CMP_N_TOTAL 0
+#define CHS_CMP_N_NAN 1
+#define CHS_CMP_N_INF 2
+#define CHS_CMP_N_BELOW 3
+#define CHS_CMP_N_UNDER 4
+#define CHS_CMP_N_OVER 5
+#define CHS_CMP_NBINS 6
+#define CHS_CMP_FWORDS 11
+#define CHS_CMP_MIN 0
+#define CHS_CMP_MAX 1
+#define CHS_CMP_SUM 2
+#define CHS_CMP_SUM_BELOW 3
+#define CHS_CMP_CENTER 4
+#define CHS_CMP_M2 5
+#define CHS_CMP_M3 6
+#define CHS_CMP_M4 7
+#define CHS_CMP_LO 8
+#define CHS_CMP_HI 9
+#define CHS_CMP_SCALE 10
+int chs_composition(chs_handle h, double threshold, int32_t nbins, double lo, double hi,
+                    int64_t iw[CHS_CMP_IWORDS], double fw[CHS_CMP_FWORDS]);   /* lo and hi both NaN: the field's own min, max */
+int chs_composition_hist(chs_handle h, int32_t nbins, int64_t* out);          /* [nbins] of the last look */
+int chs_composition_select(chs_handle h, int32_t nq, const int64_t* ranks, double* values);
+/* Device time (ms, HIP events) of the handle's last chs_composition or chs_composition_select, first launch to last. */
+int chs_composition_last_ms(chs_handle h, double* ms);
+/* The kernels' geometry: a workgroup of `threads` threads takes tiles of threads * elems_per_thread consecutive
+ * elements, every max_groups-th one where the field has more tiles than that; the digits of the radix select have
+ * digit_bits bits.  A thread adds E = elems_per_thread * ceil(tiles / groups) elements one after the other, with tiles =
+ * ceil(N^2 / (threads * elems_per_thread)) and groups = min(tiles, max_groups); the trees above it are
+ * D = log2(threads) + ceil(log2(max_groups)) deep. */
+int chs_composition_tile(int32_t* elems_per_thread, int32_t* threads, int32_t* max_groups, int32_t* digit_bits);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -508,6 +576,15 @@ int chs_batch_distance_map(chs_batch b, int32_t* out);
  * member's single handle on the same field.  The members' states, fields and records stay untouched. */
 int chs_batch_chords(chs_batch b, int32_t member, double threshold, int64_t out[CHS_CH_WORDS]);
 int chs_batch_chords_hist(chs_batch b, int32_t nbins, int64_t* out);
+/* chs_composition and chs_composition_select of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one
+ * set of buffers for the batch, so the histogram and the time are those of the batch's last look, whichever member it
+ * was.  Words, histogram and values are those of the member's single handle on the same field.  The members' states,
+ * fields and records stay untouched.  (The geometry has no handle: chs_composition_tile.) */
+int chs_batch_composition(chs_batch b, int32_t member, double threshold, int32_t nbins, double lo, double hi,
+                          int64_t iw[CHS_CMP_IWORDS], double fw[CHS_CMP_FWORDS]);
+int chs_batch_composition_hist(chs_batch b, int32_t nbins, int64_t* out);
+int chs_batch_composition_select(chs_batch b, int32_t member, int32_t nq, const int64_t* ranks, double* values);
+int chs_batch_composition_last_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }
