@@ -41,7 +41,7 @@ DTYPES = {'float64': CHS_F64, 'f64': CHS_F64, 'float32': CHS_F32, 'f32': CHS_F32
 # every symbol include/chs_hip.h declares
 SYMBOLS = (
     'chs_create', 'chs_destroy', 'chs_pool_clear', 'chs_pool_count', 'chs_set_U', 'chs_init_U_pcg64', 'chs_get_U', 'chs_prepare', 'chs_step_n',
-    'chs_get_state', 'chs_set_state', 'chs_set_jitter_noise', 'chs_set_jitter_pcg64', 'chs_dctn', 'chs_get_mu', 'chs_test_math',
+    'chs_get_state', 'chs_set_state', 'chs_set_jitter_noise', 'chs_set_jitter_pcg64', 'chs_dctn', 'chs_get_mu', 'chs_test_math', 'chs_test_math_cols',
     'chs_engine', 'chs_kernel_name', 'chs_profile_steps', 'chs_last_step_ms',
     'chs_last_error', 'chs_version',
     'chs_batch_create', 'chs_batch_destroy', 'chs_batch_set_U', 'chs_batch_init_U_pcg64', 'chs_batch_get_U',
@@ -151,6 +151,7 @@ def load():
     lib.chs_get_mu.argtypes = [C.c_void_p, dp]
     lib.chs_engine.argtypes = [C.c_void_p]
     lib.chs_test_math.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_int64]
+    lib.chs_test_math_cols.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_int64]
     lib.chs_kernel_name.argtypes = [C.c_void_p, C.c_int]
     lib.chs_kernel_name.restype = C.c_char_p
     lib.chs_profile_steps.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_int64)]
@@ -329,6 +330,44 @@ def test_math(which, a, b=None, device=0):
     if rc != CHS_OK:
         raise EngineError(f"chs_test_math failed ({rc}): {lib.chs_last_error().decode()}")
     return out
+
+
+# codes of chs_test_math_cols (include/chs_hip.h)
+MATH_DIV_POS, MATH_DIV_POS1 = 10, 11
+MATH_EMU_BOTH, MATH_EMU_ENERGY, MATH_EMU_MU = 12, 13, 14
+MATH_CHAIN, MATH_CHAIN_DOM = 15, 16
+MATH_E_LOGS, MATH_MU_LOGS, MATH_E_LOGS_FAST, MATH_MU_LOGS_FAST = 17, 18, 19, 20
+MATH_E_LOGS_F32, MATH_MU_LOGS_F32, MATH_E_LOGS_FAST_F32, MATH_MU_LOGS_FAST_F32 = 21, 22, 23, 24
+MATH_DT, MATH_DT_FAST, MATH_DT_FAST_F32 = 25, 26, 27
+MATH_SPECTRAL, MATH_SPECTRAL_F32IO, MATH_SPECTRAL_F32 = 28, 29, 30
+MATH_LOGF, MATH_LOG_RATIO_F32, MATH_MU_F32, MATH_ENERGY_F32 = 31, 32, 33, 34
+MATH_LOG_TAB_F32, MATH_LOG_TAB = 35, 36
+MATH_F32_CODES = (21, 22, 23, 24, 27, 31, 32, 33, 34, 35)   # every input and constant is a float value
+MATH_F32_IO_CODES = (29, 30)                                # in0, in1 are float values; li, lj, lam1, lam2 stay double
+
+
+def test_math_cols(which, cols, consts=(), device=0):
+    """One inline function of chs_math.h elementwise on the device: chs_test_math_cols in include/chs_hip.h.  `cols`:
+    up to four equally long input columns, `consts`: up to eight uniform constants; returns the two output columns.
+    The fp32 codes get every input rounded to float here, so that the device's conversion is exact."""
+    lib = load()
+    cols = [np.ascontiguousarray(c, dtype=np.float64).ravel() for c in cols]
+    if not 1 <= len(cols) <= 4 or any(c.size != cols[0].size for c in cols) or len(consts) > 8:
+        raise ValueError("one to four input columns of one length and at most eight constants")
+    n = cols[0].size
+    k = np.zeros(8)
+    k[:len(consts)] = consts
+    nf32 = 4 if which in MATH_F32_CODES else 2 if which in MATH_F32_IO_CODES else 0
+    if which in MATH_F32_CODES:
+        k = k.astype(np.float32).astype(np.float64)
+    buf = np.zeros((4, max(n, 1)))
+    for j, c in enumerate(cols):
+        buf[j, :n] = c.astype(np.float32).astype(np.float64) if j < nf32 else c
+    out = np.empty((2, max(n, 1)))
+    rc = lib.chs_test_math_cols(device, which, _dptr(buf), _dptr(k), _dptr(out), n)
+    if rc != CHS_OK:
+        raise EngineError(f"chs_test_math_cols failed ({rc}): {lib.chs_last_error().decode()}")
+    return out[0], out[1]
 
 
 class _Looks:

@@ -21,7 +21,10 @@
 #define CHS_SQRT2 1.4142135623730951
 #define CHS_SQRT1_2 0.7071067811865476
 
-// d / sig for sig in [0.5, 4): hardware reciprocal + two Newton steps + one residual correction
+// d / sig for sig > 0: hardware reciprocal + two Newton steps + one residual correction.  The result is under 1 ulp
+// from the exact quotient (tests/test_gpu_math.py) over the two ranges the callers ask for: sig in [0.5, 4) (the
+// logarithms below) and sig = CHeig in [1, 1.3e11] (chs_spectral through chs_div_pos1: every N up to 16384 at every
+// time step up to N * delt_max), d in +-[2^-60, 2^60].
 __device__ __forceinline__ double chs_div_pos(double d, double sig) {
   double r = __builtin_amdgcn_rcp(sig);
   double e = __builtin_fma(-sig, r, 1.0);
@@ -160,6 +163,9 @@ template <> __device__ __forceinline__ double chs_log_pos<double>(double x) { re
 template <> __device__ __forceinline__ float chs_log_pos<float>(float x) { return chs_logf(x); }
 template <typename T> __device__ __forceinline__ T chs_log_unit_tab(T x, const double2* tab, unsigned& domain);
 template <> __device__ __forceinline__ double chs_log_unit_tab<double>(double x, const double2* tab, unsigned& domain) { return chs_log_unit_tab_f64(x, tab, domain); }
+// fp32: the domain word flags every x that is not positive (0, negative, NaN).  x = 1 and x = +inf are arguments of the
+// log like any other (0 and +inf come back); the row kernels pass both U and 1 - U, so a field value of 1 or inf is
+// flagged through the other argument (tests/test_gpu_math.py).
 template <> __device__ __forceinline__ float chs_log_unit_tab<float>(float x, const double2*, unsigned& domain) {
   domain = max(domain, (x > 0.0f) ? 0u : ~0u);
   return chs_logf(x);
@@ -286,7 +292,10 @@ __device__ __forceinline__ double chs_dt_integrand(double mu, double delt_max) {
 // The same integrand where it is evaluated for every grid point of every second step (the fused row kernel): a
 // reciprocal square root instead of a square root and a division.  fp64: v_rsq_f64 refined by two Newton steps
 // (~2 ulp; the column sums agree with the oracle's to 1e-15); fp32 engine: the hardware's v_rsq_f32 (1 ulp), in the
-// precision of its operand mu.
+// precision of its operand mu.  Measured against the exact integrand over mu in +-[1e-8, 1e8] (tests/test_gpu_math.py,
+// profiles/math_pointwise.txt): 2.6 ulp (fp64), 2.1 ulp (fp32); mu = 0 gives delt_max exactly in both.  An infinite mu
+// gives 0 in the literal form and in the fp32 form but NaN in the fp64 form (rsq(inf) = 0 times h = inf in the Newton
+// step); NaN stays NaN in all three.  An infinite mu only arises from a field that has already tripped the NaN record.
 __device__ __forceinline__ double chs_dt_integrand_fast(double mu, double delt_max) {
   const double a = __builtin_fma(62.5 * mu, mu, 1.0);
   const double h = 0.5 * a;

@@ -220,6 +220,38 @@ int chs_get_mu(chs_handle h, double* host_mu);
  *         4: log(a) for a > 0 (division-based variant)
  *         5: log(a) for a > 0, table-driven (the variant the fused row kernel uses) */
 int chs_test_math(int device, int which, const double* a, const double* b, double* out, int64_t n);
+/* The other inline functions of chs_math.h, each called elementwise as the step kernels call it (accuracy tests).
+ * `in` holds four input columns of n doubles each (column c at in + c*n; a column a code does not read may hold
+ * anything), `consts` eight uniform constants, `out` receives two output columns of n doubles (out1 is 0 where a code
+ * has one result).  The physics codes read consts = {RT, B, BRT, A0, A1, sE0}.  The fp32 codes convert every input
+ * and constant to float first -- exact when the caller has rounded them to float -- compute in float and return the
+ * result widened to double.  A domain word is returned as what chs_log_dom_bad says of it, 0 or 1, never folded into NaN.
+ *   which  function                                       in0..in3         out0, out1
+ *   10     chs_div_pos                                    d, sig           quotient, the reciprocal seed rcp(sig)
+ *   11     chs_div_pos1                                   d, sig           quotient, the reciprocal seed rcp(sig)
+ *   12     chs_energy_mu_from_logs<true, true>            U, Uinv, lU, lV  sE (from sE0), mu
+ *   13     chs_energy_mu_from_logs<true, false>           U, Uinv, lU, lV  sE (from sE0), 0
+ *   14     chs_energy_mu_from_logs<false, true>           U, Uinv, lU, lV  sE0 untouched, mu
+ *   15     one point of the fused fp64 row kernel:        u                sE (from sE0), mu
+ *          uinv = 1 - u, two chs_log_unit_tab_f64, chs_energy_mu_from_logs<true, true>
+ *   16     the same chain                                 u                mu, domain word bad
+ *   17/18  chs_energy_from_logs / chs_mu_from_logs <double>        U, Uinv, lU, lV  value
+ *   19/20  chs_energy_from_logs_fast / chs_mu_from_logs_fast <double>   "            value
+ *   21-24  the four of 17-20 in <float>                                "            value
+ *   25     chs_dt_integrand, delt_max = consts[0]         mu               value
+ *   26     chs_dt_integrand_fast, the double form, the same arguments
+ *   27     chs_dt_integrand_fast, the float form, the same arguments
+ *   28     chs_spectral<double>, lam1 = consts[0], lam2 = consts[1]   hatU, hatMu, li, lj   value
+ *   29     chs_spectral<float, false>, the same arguments
+ *   30     chs_spectral_f32, the same arguments
+ *   31     chs_logf                                       x                value
+ *   32     chs_log_ratio<float>                           a, b             value
+ *   33     chs_mu<float>                                  U                value
+ *   34     chs_energy_density<float>                      U                value
+ *   35     chs_log_unit_tab<float>                        x                value, domain word bad
+ *   36     chs_log_unit_tab<double>                       x                value, domain word bad
+ * CHS_EINVAL for a null argument, n outside [1, 2^28] or another code. */
+int chs_test_math_cols(int device, int which, const double* in, const double* consts, double* out, int64_t n);
 /* Which engine the handle resolved to (CHS_ENGINE_DIRECT / CHS_ENGINE_FAST / CHS_ENGINE_CHIRP). */
 int chs_engine(chs_handle h);
 

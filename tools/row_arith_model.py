@@ -1,73 +1,21 @@
 #!/usr/bin/env python3
-"""Executable model of the fp64 pointwise block of the row kernels (chsimpy_amd/csrc/chs_math.h:
-chs_log_unit_tab_f64 and chs_energy_mu_from_logs), operation by operation with an exact fused multiply-add
-(rational arithmetic, rounded once), set against the oracle's numpy expressions.  No GPU needed.
+"""The executable model of the fp64 pointwise block of the row kernels (oracle/math_model.py: chs_log_unit_tab_f64 and
+chs_energy_mu_from_logs of chsimpy_amd/csrc/chs_math.h, operation by operation with an exact fused multiply-add,
+rounded once), set against the oracle's numpy expressions.  No GPU needed.
 
 usage: tools/row_arith_model.py [points]
 Prints the largest error of the modelled log in ulp, and the largest relative difference of the energy density and
 of EnergieEut from the oracle's expressions over the ramp U = 1e-6 .. 1-1e-6 (where U log U + (1-U) log(1-U) cancels
 worst) and over the usual field 0.875 +- 0.01 (profiles/row_arith_parity_margins.txt)."""
 import os
-import re
-import struct
 import sys
-from fractions import Fraction
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import chs_oracle as orc  # noqa: E402
-
-LN2 = 0.6931471805599453
-DOM_MAX = 0x100FFF
-
-
-def fma(a, b, c):
-    return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def table():
-    txt = open(os.path.join(ROOT, 'chsimpy_amd', 'csrc', 'chs_log_table.h')).read()
-    rows = re.findall(r'\{(-?0x[0-9a-f.]+p[+-]\d+), (-?0x[0-9a-f.]+p[+-]\d+)\}', txt)
-    assert len(rows) == 129
-    return [(float.fromhex(a), float.fromhex(b)) for a, b in rows]
-
-
-TAB = table()
-
-
-def log_unit_tab(x):
-    m, e = np.frexp(x)
-    m, e = float(m), int(e)
-    hi = struct.unpack('<II', struct.pack('<d', m))[1]
-    w = (hi - (0x3FE00000 - 0x1000)) & 0xFFFFFFFF
-    assert w <= DOM_MAX
-    rc, lc = TAB[min(w, DOM_MAX) >> 13]
-    r = fma(m, rc, -1.0)
-    p = fma(r, -1.0 / 6.0, 1.0 / 5.0)
-    p = fma(r, p, -1.0 / 4.0)
-    p = fma(r, p, 1.0 / 3.0)
-    p = fma(r, p, -0.5)
-    q = fma(r, p, 1.0)
-    return fma(r, q, fma(float(e), LN2, lc))
-
-
-def energy_mu(U, o):
-    """(E, mu) of one point as chs_energy_mu_from_logs<true, true> forms them (E: the two fmas onto a zero sum)."""
-    RT, A0, A1, B, BRT = o.RT, o.A0, o.A1, o.params.B, o.BRT
-    A1h, nRTB, c0 = 1.5 * A1, -(RT * B), -(BRT + 0.5 * A1)
-    Uinv = 1.0 - U
-    lU, lV = log_unit_tab(U), log_unit_tab(Uinv)
-    V2 = Uinv - U
-    d = lU - lV
-    g = fma(A1, V2, A0)
-    t = fma(g, Uinv, nRTB)
-    s = fma(U, d, lV)
-    E = fma(U, t, fma(RT, s, 0.0))
-    h = fma(A1h, V2, A0)
-    m = fma(RT, d, c0)
-    return E, fma(V2, h, m)
+from oracle.math_model import energy_mu, log_unit_tab  # noqa: E402  (the model itself: shared with the tests)
 
 
 def margins(U, o):
