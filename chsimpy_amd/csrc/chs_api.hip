@@ -570,7 +570,7 @@ static int run_steps(Engine* E, int64_t nsteps, int flags, double* rows, int64_t
   CallFacts f;
   f.adaptive = E->dc.adaptive_time != 0; f.full_sim = E->dc.full_sim != 0; f.time_limit_s = E->dc.time_limit_s; f.N = E->N;
   f.fused = (E->engine == CHS_ENGINE_FAST) && !chs_jitter_on(E);
-  f.fusedAdapt = E->fusedAdapt; f.partRows = E->dPartColRows != nullptr; f.twoSets = E->partSet[0][0] != nullptr;
+  f.fusedAdapt = E->fusedAdapt; f.partRows = E->dPartColRows != nullptr; f.twoSets = E->part[1].diag != nullptr;
   f.adaptSparse = E->adaptSparse; f.lamByColmin = E->lamByColmin; f.gateEarly = E->gateEarly;
   f.profile = profile;
   f.carry_hat = (flags & CHS_STEP_CARRY_HAT) != 0; f.rederive = (flags & CHS_STEP_REDERIVE_HAT) != 0;

@@ -428,7 +428,7 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
     E->hat_valid = true;
     r.dc = E->dc;
     r.arr[NAT_U] = E->dU; r.arr[NAT_MU] = E->dMU; r.arr[NAT_T1] = E->dT1; r.arr[NAT_T2] = E->dT2; r.arr[NAT_HAT] = E->dHat;
-    r.partMu = E->dPartMu; r.partDiag = E->dPartDiag;
+    r.partMu = E->sums().mu; r.partDiag = E->sums().diag;
     r.rows = E->dRows; r.rowsCap = E->rowsCap;
   }
   for (int i = 0; !b->chirp && i < B; ++i) {
@@ -445,18 +445,19 @@ int call_enter(BatchCall& c, int32_t flags, int32_t seats) {
     c.cs0[(size_t)i] = E->csHost;
     if (chs_stop_armed(E)) c.batch_steps = E->batchSteps < c.batch_steps ? E->batchSteps : c.batch_steps;
     if ((rc = chs_launch_call_begin(E))) return rc;
-    if ((rc = chs_fast_enter_fused(E))) return rc;   // (selects the partial-sum set the whole call uses)
+    if ((rc = chs_fast_enter_fused(E))) return rc;
     E->hat_valid = true;
     r.dc = E->dc;
     r.T1 = E->dT1;
     r.T2 = E->dT1;
     r.hat = E->dHat;
     r.U = E->dU;
-    r.partDiag = E->dPartDiag; r.partMu = E->dPartMu; r.partRa = E->dPartRa; r.partE2 = E->dPartE2;
-    r.tail[0] = chs_tail_args(E, -1, 1);
+    const PartialSums& ps = E->sums();   // one set for the whole call: the batch's tail runs in stream order
+    r.partDiag = ps.diag; r.partMu = ps.mu; r.partRa = ps.ra; r.partE2 = ps.e2;
+    r.tail[0] = chs_tail_args(E, ps, 1);
     r.tail[0].pre_only = 1;
-    r.tail[1] = chs_tail_args(E, -1, 1);
-    r.tail[2] = chs_tail_args(E, -1, 0);
+    r.tail[1] = chs_tail_args(E, ps, 1);
+    r.tail[2] = chs_tail_args(E, ps, 0);
     if (c.adaptive) {
       // the first step's time-step control as the single handle runs it: the integrand's column sums from a sweep of
       // U (the rule looks at the counter as the previous call left it), then k_pre -- once per call

@@ -210,6 +210,14 @@ struct StepTimer {
   hipEvent_t cur = nullptr;      // start event of the open span
 };
 
+// The partial sums a step leaves for its record and for the time-step control of the next step.
+struct PartialSums {
+  double* diag = nullptr;  // per-block [sE, sG, sPS, cSA]
+  double* mu = nullptr;    // per-block sum(mu^2)
+  double* e2 = nullptr;    // per-column-tile spectral gradient sums (fast engine)
+  double* ra = nullptr;    // Ra of the step, written by the row kernel (fast engine)
+};
+
 #define CHS_STAGE_BYTES (8u << 20)
 struct Engine {
   // two pinned staging chunks of this handle for field up/downloads (allocated at the first transfer)
@@ -257,14 +265,10 @@ struct Engine {
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
-  double* dPartMu = nullptr;   // per-block sum(mu^2)
   double* dPartCol = nullptr;  // per-band column sums for the adaptive step
   double* dPartColMin = nullptr;
-  double* dPartDiag = nullptr; // per-block [sE, sG, sPS, cSA]
   double* dPartSum = nullptr;  // per-block sum(U)
-  double* dPartE2 = nullptr;   // per-column-tile spectral gradient sums (fast engine)
   double* dSinSq = nullptr;    // sin^2(pi k/N), k = 0..N-1 (fast engine)
-  double* dPartRa = nullptr;   // Ra of the step, written by the row kernel (fast engine)
   int nPartE2 = 0;
   int nRowBlocks = 0;          // workgroups of the fast row kernels (diag partials)
   int nBands = 0;              // row bands used by the pointwise kernels
@@ -274,10 +278,20 @@ struct Engine {
   int nColMinBlocks = 0;
   int nColMinCur = 0;  // entries of dPartColMin the last column-sum launch wrote
 
-  // deferred tail: the bookkeeping of step s rides as one extra workgroup in k_col of step s+1;
-  // the partial sums ping-pong between two sets so that step s+1 does not overwrite what it reads
-  double* partSet[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};  // Diag, Mu, E2, Ra
-  int parity = 0;
+  // The partial sums.  The natural engines have set 0 alone (chs_pointwise_alloc).  The fast engine has two
+  // (chs_fast_init): the bookkeeping of step s rides as one extra workgroup in k_col of step s+1, and the sums
+  // ping-pong between the sets so that step s+1 does not overwrite what that workgroup reads.  Both are freed by
+  // chs_pointwise_free.
+  PartialSums part[2];
+  int parity = 0;             // the set the running step writes; always 0 without the second set
+  // Every kernel launched outside a riding tail takes its partial sums from here.  `parity` flips only behind a step
+  // whose tail rides (chs_fast_step), and the next thing to touch the sums is then the next step of the same call: a
+  // call's last step runs its tail at once (StepIssue::tail_now) and never flips.  So everything between two calls
+  // -- prepare's k_diag / k_fin pair, the entry of the next call, the batch's call_enter behind chs_fast_enter_fused
+  // -- sees the set that the last step wrote; a call that a stop cut short leaves nothing in either set that is
+  // read again (Engine::resident is off then).
+  PartialSums& sums() { return part[parity]; }
+  const PartialSums& sums() const { return part[parity]; }
   PendingTail pending;        // the tail of the previous step of the running call, where it is still to run (chs_fast_step)
   unsigned long long gateSeq = 0;
   bool testGateWithhold = false;  // test hook (CHS_TEST_GATE_WITHHOLD=1, read by chs_step_n in builds with -DCHS_TEST_HOOKS=1): gated tails never publish
@@ -298,7 +312,6 @@ struct Engine {
   int batchSteps = 1024;      // steps issued between two looks at the device's halt flag (run_steps)
   double lastStepMs = 0.0;
   StepTimer timer;
-  std::vector<double> hostTmp;
   std::vector<double> hLambda;  // the eigenvalue table the engine was created with (engine pool: chs_create)
 };
 
@@ -337,7 +350,7 @@ struct BatchMember;
 // the batch's column-minimum reduction: the members' partial rows (chs_fast_kernels.h: k_row_inv<ADAPT>) -> partColMin
 int chs_colmin_batch_buffers(Engine* E, BatchMember* r);
 int chs_launch_colmin_rows_batch(hipStream_t s, const BatchMember* mem, int B, int N, bool rows_f32);
-TailArgs chs_tail_args(const Engine* E, int set, int do_pre);  // set < 0: the current partial-sum pointers
+TailArgs chs_tail_args(const Engine* E, const PartialSums& sums, int do_pre);
 int chs_launch_step_tail(Engine* E, int do_pre);  // fused pipeline: record of step s + time-step control of step s+1
 int chs_launch_pre(Engine* E);                // partials -> state (L2, delt, time)
 int chs_launch_call_begin(Engine* E);         // entry of a solve_or_resume call: re-arm the loop, coefficients of params.delt

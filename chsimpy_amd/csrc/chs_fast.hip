@@ -104,14 +104,18 @@ int chs_fast_init(Engine* E) {
   E->nRowBlocks = E->N / (P->threads / P->G);
   E->nPartMu = E->nRowBlocks;
   E->nPartE2 = P->col_tiles;
-  CHS_HIP(hipMalloc(&E->dPartE2, sizeof(double) * (size_t)E->nPartE2));
-  CHS_HIP(hipMalloc(&E->dPartRa, sizeof(double) * 8));
-  // second set of partial sums for the deferred tail (chs_fast_step)
-  E->partSet[0][0] = E->dPartDiag; E->partSet[0][1] = E->dPartMu; E->partSet[0][2] = E->dPartE2; E->partSet[0][3] = E->dPartRa;
-  CHS_HIP(hipMalloc(&E->partSet[1][0], sizeof(double) * 4 * (size_t)(E->nDiagBlocks > E->N ? E->nDiagBlocks : E->N)));
-  CHS_HIP(hipMalloc(&E->partSet[1][1], sizeof(double) * (size_t)(E->nBands > E->N ? E->nBands : E->N)));
-  CHS_HIP(hipMalloc(&E->partSet[1][2], sizeof(double) * (size_t)E->nPartE2));
-  CHS_HIP(hipMalloc(&E->partSet[1][3], sizeof(double) * 8));
+  // Two sets of partial sums, for the deferred tail (Engine::part).  Either set can be the current one when the
+  // pointwise kernels run on this engine (prepare's k_diag, chs_get_mu's k_mu), so both hold the larger of their
+  // block counts and the row kernels' (at most N workgroups); set 0 comes from chs_pointwise_alloc at its sizes.
+  const size_t nDiag = (size_t)(E->nDiagBlocks > E->N ? E->nDiagBlocks : E->N), nMu = (size_t)(E->nBands > E->N ? E->nBands : E->N);
+  for (PartialSums& p : E->part) {
+    hipFree(p.diag); hipFree(p.mu);
+    p = PartialSums();
+    CHS_HIP(hipMalloc(&p.diag, sizeof(double) * 4 * nDiag));
+    CHS_HIP(hipMalloc(&p.mu, sizeof(double) * nMu));
+    CHS_HIP(hipMalloc(&p.e2, sizeof(double) * (size_t)E->nPartE2));
+    CHS_HIP(hipMalloc(&p.ra, sizeof(double) * 8));
+  }
   return chs_fast_rearm(E);
 }
 
@@ -126,10 +130,6 @@ int chs_fast_rearm(Engine* E) {
   { const char* e = getenv("CHS_LAM_BY_COLMIN"); E->lamByColmin = !(e && e[0] == '0'); }
   if (E->dc.adaptive_time && E->fusedAdapt && !E->dPartColRows)
     CHS_HIP(hipMalloc(&E->dPartColRows, E->esz * (size_t)E->nRowBlocks * E->N));
-  if (E->partSet[0][0]) {
-    E->dPartDiag = E->partSet[0][0]; E->dPartMu = E->partSet[0][1];
-    E->dPartE2 = E->partSet[0][2]; E->dPartRa = E->partSet[0][3];
-  }
   E->parity = 0;
   E->stepCount = 0;
   return CHS_OK;
@@ -140,18 +140,9 @@ void chs_fast_free(Engine* E) {
   if (!P) return;
   if (P->tables) hipFree(P->tables);
   if (E->dSinSq) hipFree(E->dSinSq);
-  // the "current" pointers alias one of the two sets: hand set 0 back to the generic owners
-  if (E->partSet[0][0]) {
-    E->dPartDiag = E->partSet[0][0]; E->dPartMu = E->partSet[0][1];
-    E->dPartE2 = E->partSet[0][2]; E->dPartRa = E->partSet[0][3];
-    for (int i = 0; i < 4; ++i) { hipFree(E->partSet[1][i]); E->partSet[1][i] = nullptr; E->partSet[0][i] = nullptr; }
-  }
   if (E->dPartColRows) hipFree(E->dPartColRows);
   E->dPartColRows = nullptr;
-  if (E->dPartE2) hipFree(E->dPartE2);
-  if (E->dPartRa) hipFree(E->dPartRa);
-  E->dPartRa = nullptr;
-  E->dSinSq = nullptr; E->dPartE2 = nullptr;
+  E->dSinSq = nullptr;
   delete P;
   E->dTw = nullptr;
 }
@@ -193,21 +184,10 @@ int chs_fast_enter(Engine* E) {
   return P->col(E, MODE_FWD_NATIVE, E->dT1, nullptr, E->dHat, nullptr, no_rider());
 }
 
-// T1 <- row DCT-II of EnergieEut(U): what the fused row kernel of the previous step would
-// have left behind; needed once per solve_or_resume call.
-// the set of partial-sum buffers the kernels of the running step write to
-static void select_partial_set(Engine* E) {
-  if (!E->partSet[0][0]) return;
-  const int par = E->parity;
-  E->dPartDiag = E->partSet[par][0]; E->dPartMu = E->partSet[par][1];
-  E->dPartE2 = E->partSet[par][2]; E->dPartRa = E->partSet[par][3];
-}
-
 // Entry of a call on the fused pipeline: hat_U <- dctn(U) (solver.py:159) and the prologue below with
 // one sweep of U instead of two (k_row_fwd2), the row transform of U parked in the idle T2 buffer.
 int chs_fast_enter_fused(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
-  select_partial_set(E);
   int rc;
   chs_slot_begin(E, SLOT_MU);
   rc = P->row_fwd2(E, E->dU, E->dT2, E->dT1);
@@ -235,9 +215,10 @@ int chs_fast_enter_hat(Engine* E) {
   return P->col(E, MODE_FWD_NATIVE, E->dT2, nullptr, E->dHat, nullptr, no_rider());
 }
 
+// T1 <- row DCT-II of EnergieEut(U): what the fused row kernel of the previous step would
+// have left behind; needed once per solve_or_resume call.
 int chs_fast_prologue(Engine* E) {
   FastPlan* P = (FastPlan*)E->dTw;
-  select_partial_set(E);  // sum(mu^2) must land where the first step's k_pre looks for it
   chs_slot_begin(E, SLOT_MU);
   const int rc = P->row_fwd(E, E->dU, E->dT1, ROW_FWD_POINTWISE);
   chs_slot_end(E, SLOT_MU);
@@ -253,7 +234,6 @@ int chs_fast_step(Engine* E, const StepMode& mode, bool first, bool last) {
   FastPlan* P = (FastPlan*)E->dTw;
   int rc;
   const StepIssue p = step_issue(mode, E->csHost, first, last);
-  select_partial_set(E);
   if (p.sweep0 && (rc = chs_launch_mu_colsums(E, 0))) return rc;
   if (p.pre == PRE_LAUNCH && (rc = chs_launch_pre(E))) return rc;
   // the extra workgroup of this step's k_col: the first step's time-step control or the previous step's tail

@@ -1440,35 +1440,36 @@ struct Launch {
     const int grid = C::N / C::C;
     if (mode == ROW_FWD_POINTWISE)
       k_row_fwd<C, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)in, (T*)out, get_tables<T>(E), E->dc, E->dState,
-                                                            E->dPartMu);
+                                                            E->sums().mu);
     else
       k_row_fwd<C, false><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)in, (T*)out, get_tables<T>(E), E->dc, E->dState,
-                                                             E->dPartMu);
+                                                             E->sums().mu);
     CHS_HIP(hipGetLastError());
     return CHS_OK;
   }
   static int row_fwd2(Engine* E, const void* in, void* ta, void* t1) {
     k_row_fwd2<C><<<C::N / C::C, C::THREADS, row_lds, E->stream>>>((const T*)in, (T*)ta, (T*)t1, get_tables<T>(E), E->dc,
-                                                                E->dState, E->dPartMu);
+                                                                E->dState, E->sums().mu);
     CHS_HIP(hipGetLastError());
     return CHS_OK;
   }
   static int row_inv(Engine* E, int mode, const void* t2, void* u, void* t1, int store_u) {
     const int grid = C::N / C::C;
     const FTables<T> tb = get_tables<T>(E);
+    const PartialSums& ps = E->sums();
     if (mode == ROW_INV_PLAIN)
       k_row_inv<C, false, false><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)t2, (T*)u, (T*)t1, tb, E->dc, E->dState,
-                                                                    E->dPartDiag, E->dPartMu, E->dPartRa, 1);
+                                                                    ps.diag, ps.mu, ps.ra, 1);
     else if (mode == ROW_INV_DIAG)
       k_row_inv<C, true, false><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)t2, (T*)u, (T*)t1, tb, E->dc, E->dState,
-                                                                   E->dPartDiag, E->dPartMu, E->dPartRa, 1);
+                                                                   ps.diag, ps.mu, ps.ra, 1);
     else if (mode == ROW_INV_FUSED)
       k_row_inv<C, true, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)t2, (T*)u, (T*)t1, tb, E->dc, E->dState,
-                                                                  E->dPartDiag, E->dPartMu, E->dPartRa, store_u);
+                                                                  ps.diag, ps.mu, ps.ra, store_u);
     else {
       if constexpr (ADAPT_OK)
         k_row_inv<C, true, true, true><<<grid, C::THREADS, row_lds, E->stream>>>((const T*)t2, (T*)u, (T*)t1, tb, E->dc, E->dState,
-                                                                          E->dPartDiag, E->dPartMu, E->dPartRa, store_u, (T*)E->dPartColRows);
+                                                                          ps.diag, ps.mu, ps.ra, store_u, (T*)E->dPartColRows);
       else { chs_set_error("fused adaptive row kernel is not built for this configuration"); return CHS_EINVAL; }
     }
     CHS_HIP(hipGetLastError());
@@ -1482,7 +1483,7 @@ struct Launch {
       case MODE_STEP: {
         int g = grid;
         if (rider.tail.any) {
-          ta = chs_tail_args(E, rider.tail.set, 1);
+          ta = chs_tail_args(E, E->part[rider.tail.set], 1);
           g = grid + 1;
           if (rider.tail.gated) {
             ta.gate = 1; ta.seq = ++E->gateSeq;
@@ -1490,26 +1491,26 @@ struct Launch {
             ta.early = rider.tail.early ? 1 : 0;
           }
         } else if (rider.pre_only) {
-          ta = chs_tail_args(E, -1, 1);
+          ta = chs_tail_args(E, E->sums(), 1);
           ta.pre_only = 1;
           g = grid + 1;
         }
         ta.reverse = (E->stepCount & 1) ? 1 : 0;
         ++E->stepCount;
-        k_col<CC, MODE_STEP><<<g, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
+        k_col<CC, MODE_STEP><<<g, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->sums().e2, ta);
         break;
       }
       case MODE_FWD_NATIVE:
-        k_col<CC, MODE_FWD_NATIVE><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
+        k_col<CC, MODE_FWD_NATIVE><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->sums().e2, ta);
         break;
       case MODE_FWD_NATURAL:
-        k_col<CC, MODE_FWD_NATURAL><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
+        k_col<CC, MODE_FWD_NATURAL><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->sums().e2, ta);
         break;
       case MODE_INV_NATIVE:
-        k_col<CC, MODE_INV_NATIVE><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
+        k_col<CC, MODE_INV_NATIVE><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->sums().e2, ta);
         break;
       default:
-        k_col<CC, MODE_INV_NATURAL><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->dPartE2, ta);
+        k_col<CC, MODE_INV_NATURAL><<<grid, CC::THREADS, col_lds, E->stream>>>((const T*)tin, (T*)tout, (T*)hat, (T*)nat, tb, E->dLambda, E->dSinSq, E->dState, E->sums().e2, ta);
         break;
     }
     CHS_HIP(hipGetLastError());

@@ -340,15 +340,11 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_step_tail(TailArgs ta, DevStat
   step_tail_body<TAIL_THREADS>(ta, st, red);
 }
 
-TailArgs chs_tail_args(const Engine* E, int set, int do_pre) {
+TailArgs chs_tail_args(const Engine* E, const PartialSums& sums, int do_pre) {
   TailArgs ta;
   ta.enabled = 1; ta.do_pre = do_pre;
   ta.dc = E->dc;
-  const bool pp = E->partSet[0][0] != nullptr && set >= 0;
-  ta.partDiag = pp ? E->partSet[set][0] : E->dPartDiag;
-  ta.partMu = pp ? E->partSet[set][1] : E->dPartMu;
-  ta.partE2 = pp ? E->partSet[set][2] : E->dPartE2;
-  ta.partRa = pp ? E->partSet[set][3] : E->dPartRa;
+  ta.partDiag = sums.diag; ta.partMu = sums.mu; ta.partE2 = sums.e2; ta.partRa = sums.ra;
   ta.partColMin = E->dPartColMin;
   ta.nRow = E->nRowBlocks; ta.nE2 = E->nPartE2; ta.nMu = E->nPartMu; ta.nColMin = E->nColMinCur ? E->nColMinCur : E->nColMinBlocks;
   ta.rows = E->dRows; ta.rowsCap = E->rowsCap;
@@ -358,7 +354,7 @@ TailArgs chs_tail_args(const Engine* E, int set, int do_pre) {
 
 int chs_launch_step_tail(Engine* E, int do_pre) {
   chs_slot_begin(E, SLOT_FIN);
-  k_step_tail<<<1, TAIL_THREADS, 0, E->stream>>>(chs_tail_args(E, -1, do_pre), E->dState);
+  k_step_tail<<<1, TAIL_THREADS, 0, E->stream>>>(chs_tail_args(E, E->sums(), do_pre), E->dState);
   chs_slot_end(E, SLOT_FIN);
   CHS_HIP(hipGetLastError());
   return CHS_OK;
@@ -501,16 +497,21 @@ int chs_pointwise_alloc(Engine* E) {
   E->nPartMu = E->nBands;
   E->nDiagBlocks = ((N + DIAG_BAND - 1) / DIAG_BAND) * ((N + PW_THREADS - 1) / PW_THREADS);
   E->nColMinBlocks = (N + PW_THREADS - 1) / PW_THREADS;
-  CHS_HIP(hipMalloc(&E->dPartMu, sizeof(double) * (size_t)(E->nBands > N ? E->nBands : N)));
+  // set 0 of the partial sums at the sizes of k_mu and k_diag (the fast engine re-sizes it and adds set 1: chs_fast_init)
+  CHS_HIP(hipMalloc(&E->part[0].mu, sizeof(double) * (size_t)E->nBands));
   CHS_HIP(hipMalloc(&E->dPartMuAux, sizeof(double) * (size_t)E->nBands));
-  CHS_HIP(hipMalloc(&E->dPartDiag, sizeof(double) * 4 * (size_t)(E->nDiagBlocks > N ? E->nDiagBlocks : N)));
+  CHS_HIP(hipMalloc(&E->part[0].diag, sizeof(double) * 4 * (size_t)E->nDiagBlocks));
   CHS_HIP(hipMalloc(&E->dPartSum, sizeof(double) * (size_t)(E->nBands > CHS_JITTER_BLOCKS_MAX ? E->nBands : CHS_JITTER_BLOCKS_MAX)));
   CHS_HIP(hipMalloc(&E->dPartColMin, sizeof(double) * (size_t)((N + 31) / 32)));  // (k_colmin_slices writes N/256 entries)
   CHS_HIP(hipMalloc(&E->dPartCol, sizeof(double) * (size_t)E->nBands * N));
   return CHS_OK;
 }
 void chs_pointwise_free(Engine* E) {
-  hipFree(E->dPartMu); hipFree(E->dPartMuAux); hipFree(E->dPartDiag); hipFree(E->dPartSum);
+  for (PartialSums& p : E->part) {   // both sets, whoever allocated them
+    hipFree(p.diag); hipFree(p.mu); hipFree(p.e2); hipFree(p.ra);
+    p = PartialSums();
+  }
+  hipFree(E->dPartMuAux); hipFree(E->dPartSum);
   hipFree(E->dPartColMin); hipFree(E->dPartCol);
   if (E->dColSlices) { hipFree(E->dColSlices); E->dColSlices = nullptr; }
 }
@@ -520,9 +521,9 @@ int chs_launch_mu(Engine* E) {
   chs_slot_begin(E, SLOT_MU);
   DISPATCH_T(E,
     (k_mu<double><<<E->nBands, PW_THREADS, 0, E->stream>>>((const double*)E->dU, (double*)E->dMU, E->dc, E->dState,
-                                                            E->dPartMu, E->dPartCol, 0, 0)),
+                                                            E->sums().mu, E->dPartCol, 0, 0)),
     (k_mu<float><<<E->nBands, PW_THREADS, 0, E->stream>>>((const float*)E->dU, (float*)E->dMU, E->dc, E->dState,
-                                                           E->dPartMu, E->dPartCol, 0, 0)));
+                                                           E->sums().mu, E->dPartCol, 0, 0)));
   chs_slot_end(E, SLOT_MU);
   CHS_HIP(hipGetLastError());
   return CHS_OK;
@@ -758,7 +759,7 @@ int chs_launch_pre(Engine* E) {
     const int rcm = launch_colmin(E, E->dPartCol, false, E->nBands, 0);
     if (rcm) { chs_slot_end(E, SLOT_PRE); return rcm; }
   }
-  k_pre<><<<1, PW_THREADS, 0, E->stream>>>(E->dc, E->dState, E->dPartMu, E->nPartMu, E->dPartColMin,
+  k_pre<><<<1, PW_THREADS, 0, E->stream>>>(E->dc, E->dState, E->sums().mu, E->nPartMu, E->dPartColMin,
                                          E->nColMinBlocks);
   chs_slot_end(E, SLOT_PRE);
   CHS_HIP(hipGetLastError());
@@ -807,9 +808,9 @@ int chs_launch_diag(Engine* E, int ignore_halt) {
   chs_slot_begin(E, SLOT_DIAG);
   DISPATCH_T(E,
     (k_diag<double><<<grid, PW_THREADS, 0, E->stream>>>((const double*)E->dU, E->dc, E->dState,
-                                                                   E->dPartDiag, ignore_halt)),
+                                                                   E->sums().diag, ignore_halt)),
     (k_diag<float><<<grid, PW_THREADS, 0, E->stream>>>((const float*)E->dU, E->dc, E->dState,
-                                                                  E->dPartDiag, ignore_halt)));
+                                                                  E->sums().diag, ignore_halt)));
   chs_slot_end(E, SLOT_DIAG);
   CHS_HIP(hipGetLastError());
   return CHS_OK;
@@ -818,12 +819,12 @@ int chs_launch_diag(Engine* E, int ignore_halt) {
 int chs_launch_fin(Engine* E, int prepare_mode, int fused) {
   chs_slot_begin(E, SLOT_FIN);
   DISPATCH_T(E,
-    (k_fin<double><<<1, PW_THREADS, 0, E->stream>>>((const double*)E->dU, E->dc, E->dState, E->dPartDiag,
+    (k_fin<double><<<1, PW_THREADS, 0, E->stream>>>((const double*)E->dU, E->dc, E->dState, E->sums().diag,
                                                      fused ? E->nRowBlocks : E->nDiagBlocks, E->dRows, E->rowsCap,
-                                                     prepare_mode, E->dPartE2, E->nPartE2, fused)),
-    (k_fin<float><<<1, PW_THREADS, 0, E->stream>>>((const float*)E->dU, E->dc, E->dState, E->dPartDiag,
+                                                     prepare_mode, E->sums().e2, E->nPartE2, fused)),
+    (k_fin<float><<<1, PW_THREADS, 0, E->stream>>>((const float*)E->dU, E->dc, E->dState, E->sums().diag,
                                                     fused ? E->nRowBlocks : E->nDiagBlocks, E->dRows, E->rowsCap,
-                                                    prepare_mode, E->dPartE2, E->nPartE2, fused)));
+                                                    prepare_mode, E->sums().e2, E->nPartE2, fused)));
   chs_slot_end(E, SLOT_FIN);
   CHS_HIP(hipGetLastError());
   return CHS_OK;
