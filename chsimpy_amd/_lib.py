@@ -32,6 +32,9 @@ CHS_CMP_IWORDS = 7            # int64 words of chs_composition: n_total, n_nan, 
 CHS_CMP_FWORDS = 11           # its float64 words: min, max, sum, sum_below, center, m2, m3, m4, lo, hi, scale
 CHS_CMP_MAX_BINS = 4096
 CHS_CMP_MAX_RANKS = 8         # ranks of one chs_composition_select
+CHS_TP_WORDS = 8              # int64 words of chs_two_point: n, the four neighbour counts and the table's sum per phase
+CHS_TP_MAX_R = 256            # rmax of chs_two_point at most
+CHS_TP_CHUNK = 2048           # the pixels of a row that one workgroup of its pair kernel owns
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -57,6 +60,8 @@ SYMBOLS = (
     'chs_batch_chords', 'chs_batch_chords_hist',
     'chs_composition', 'chs_composition_hist', 'chs_composition_select', 'chs_composition_last_ms', 'chs_composition_tile',
     'chs_batch_composition', 'chs_batch_composition_hist', 'chs_batch_composition_select', 'chs_batch_composition_last_ms',
+    'chs_two_point_max_r', 'chs_two_point_size', 'chs_two_point', 'chs_two_point_counts', 'chs_two_point_last_ms',
+    'chs_two_point_tile', 'chs_batch_two_point', 'chs_batch_two_point_counts', 'chs_batch_two_point_last_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -217,6 +222,17 @@ def load():
     lib.chs_batch_composition_hist.argtypes = [vp, C.c_int32, i64p]
     lib.chs_batch_composition_select.argtypes = [vp, C.c_int32, C.c_int32, i64p, dp]
     lib.chs_batch_composition_last_ms.argtypes = [vp, dp]
+    lib.chs_two_point_max_r.argtypes = [C.c_int32]
+    lib.chs_two_point_max_r.restype = C.c_int32
+    lib.chs_two_point_size.argtypes = [C.c_int32, C.c_int32]
+    lib.chs_two_point_size.restype = C.c_int64
+    lib.chs_two_point.argtypes = [vp, C.c_double, C.c_int32, i64p]
+    lib.chs_two_point_counts.argtypes = [vp, C.c_int64, i64p]
+    lib.chs_two_point_last_ms.argtypes = [vp, dp]
+    lib.chs_two_point_tile.argtypes = [i32p, i32p, i32p]
+    lib.chs_batch_two_point.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, i64p]
+    lib.chs_batch_two_point_counts.argtypes = [vp, C.c_int64, i64p]
+    lib.chs_batch_two_point_last_ms.argtypes = [vp, dp]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -283,6 +299,26 @@ def chords_tile():
 def chords_bins(N):
     """The bins of each of the eight histograms of chs_chords at grid size N (chs_chords_bins)."""
     return int(load().chs_chords_bins(int(N)))
+
+
+def two_point_tile():
+    """(word_bits, band_rows, lanes) of the kernels of chs_two_point (chs_two_point_tile): the pixels of a row in one word,
+    the rows of a band of the pair kernel and the lanes of its workgroup, which owns band_rows rows of CHS_TP_CHUNK pixels."""
+    w, h, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = load().chs_two_point_tile(C.byref(w), C.byref(h), C.byref(n))
+    if rc != CHS_OK:
+        raise EngineError(f"chs_two_point_tile failed ({rc})")
+    return int(w.value), int(h.value), int(n.value)
+
+
+def two_point_max_r(N):
+    """The largest rmax of chs_two_point at grid size N (chs_two_point_max_r)."""
+    return int(load().chs_two_point_max_r(int(N)))
+
+
+def two_point_size(N, rmax):
+    """The entries of the count table of chs_two_point, 0 for arguments out of range (chs_two_point_size)."""
+    return int(load().chs_two_point_size(int(N), int(rmax)))
 
 
 def composition_tile():
@@ -472,6 +508,38 @@ class _Looks:
         """Device time (ms) of the last `composition` or `composition_select`."""
         return self._last_ms(self._prefix + 'composition_last_ms')
 
+    _tp_rmax = 0
+
+    def _two_point(self, lead, threshold, rmax):
+        out = np.empty(CHS_TP_WORDS, dtype=np.int64)
+        self._look_call('two_point', *lead, float(threshold), int(rmax), _i64ptr(out))
+        self._tp_rmax = int(rmax)
+        return out
+
+    def two_point_counts(self, rmax=None):
+        """int64 [2][rmax + 1][2 rmax + 1] of the last look: the pair counts by phase and displacement (rmax: that of the
+        last look of this object)."""
+        r = self._tp_rmax if rmax is None else int(rmax)
+        out = np.empty((2, r + 1, 2 * r + 1), dtype=np.int64)
+        self._look_call('two_point_counts', out.size, _i64ptr(out))
+        return out
+
+    def _two_point_look(self, lead, threshold, rmax, counts):
+        words = self._two_point(lead, threshold, rmax)
+        return words, (self.two_point_counts() if counts else None)
+
+    def two_point_ms(self):
+        """Device time (ms) of the last `two_point`."""
+        return self._last_ms(self._prefix + 'two_point_last_ms')
+
+    @staticmethod
+    def two_point_tile():
+        return two_point_tile()
+
+    @staticmethod
+    def two_point_max_r(N):
+        return two_point_max_r(N)
+
 
 class Engine(_Looks):
     """One device-resident simulation (an opaque ``chs_handle``)."""
@@ -639,6 +707,15 @@ class Engine(_Looks):
         """The ranks[k]-th smallest pixels (0-based, at most CHS_CMP_MAX_RANKS of them), exactly
         (chs_composition_select)."""
         return self._composition_select((), ranks)
+
+    def two_point(self, threshold, rmax):
+        """The 8 int64 summary words of the two-point correlation of the field the device holds (chs_two_point;
+        chsimpy_amd/two_point.py names them).  The count table of this look: `two_point_counts`."""
+        return self._two_point((), threshold, rmax)
+
+    def two_point_look(self, threshold, rmax, counts=True):
+        """One look with what belongs to it: (words, count table or None)."""
+        return self._two_point_look((), threshold, rmax, counts)
 
     def morphology_ms(self):
         """Device time (ms) of the last `morphology`."""
@@ -822,6 +899,13 @@ class Batch(_Looks):
     def composition_select(self, member, ranks):
         """`Engine.composition_select` of one member (chs_batch_composition_select)."""
         return self._composition_select((int(member),), ranks)
+
+    def two_point(self, member, threshold, rmax):
+        """`Engine.two_point` of one member (chs_batch_two_point)."""
+        return self._two_point((int(member),), threshold, rmax)
+
+    def two_point_look(self, member, threshold, rmax, counts=True):
+        return self._two_point_look((int(member),), threshold, rmax, counts)
 
     def get_state(self, member):
         s = chs_state()

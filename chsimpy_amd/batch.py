@@ -34,7 +34,7 @@ import functools
 
 import numpy as np
 
-from . import _lib
+from . import _lib, two_point
 from .solver import Solver
 
 
@@ -127,7 +127,7 @@ class _Member:
         return self._b.morphology(threshold, self._m)
 
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
-              'composition_look', 'composition_select')
+              'composition_look', 'composition_select', 'two_point', 'two_point_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -313,6 +313,10 @@ class BatchSolver:
     def composition(self, member=None, threshold=None, bins=15, range=None, quantiles=(0.05, 0.5, 0.95), hist=True):
         """The members' compositions (`Solver.composition`), a `composition.Composition` each: _member_by_member."""
         return self._member_by_member('composition', member, threshold, bins, range, quantiles, hist)
+
+    def two_point(self, member=None, threshold=None, rmax=two_point.DEFAULT_RMAX, counts=True):
+        """The members' two-point correlations (`Solver.two_point`), a `two_point.TwoPoint` each: _member_by_member."""
+        return self._member_by_member('two_point', member, threshold, rmax, counts)
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

@@ -166,6 +166,7 @@ struct Batch {
   void* dt = nullptr;            // chs_batch_distance: the batch's one set of buffers (chs_distance.hip), at the first look
   void* ch = nullptr;            // chs_batch_chords: the batch's one set of buffers (chs_chords.hip), at the first look
   void* cmp = nullptr;           // chs_batch_composition: the batch's one set of buffers (chs_composition.hip), at the first look
+  void* tp = nullptr;            // chs_batch_two_point: the batch's one set of buffers (chs_two_point.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -187,6 +188,7 @@ void batch_free(Batch* b) {
   chs_dt_free(&b->dt);
   chs_ch_free(&b->ch);
   chs_cmp_free(&b->cmp);
+  chs_tp_free(&b->tp);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -888,4 +890,24 @@ extern "C" int chs_batch_composition_select(chs_batch h, int32_t member, int32_t
 extern "C" int chs_batch_composition_last_ms(chs_batch h, double* ms) {
   Batch* b = as_batch(h);
   return chs_cmp_last_ms(b, b ? b->cmp : nullptr, ms, "chs_batch_composition");
+}
+
+// The two-point correlation of one member: the single handle's look on the batch's stream, with the batch's one set of
+// buffers.
+extern "C" int chs_batch_two_point(chs_batch h, int32_t member, double threshold, int32_t rmax, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_two_point: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_two_point: no such member");
+  return chs_tp_look(b->m[(size_t)member], b->stream, &b->tp, threshold, rmax, out, "chs_batch_two_point");
+}
+
+extern "C" int chs_batch_two_point_counts(chs_batch h, int64_t n, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_two_point_counts: null handle");
+  return chs_tp_counts(b->tp, b->m[0]->hc.device, b->stream, n, out, "chs_batch_two_point_counts");
+}
+
+extern "C" int chs_batch_two_point_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_tp_last_ms(b, b ? b->tp : nullptr, ms, "chs_batch_two_point");
 }

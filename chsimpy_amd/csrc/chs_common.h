@@ -262,6 +262,7 @@ struct Engine {
   void* dt = nullptr;          // distance transform: band masks, carries, D2, histogram, result, events (chs_distance.hip), at the first look
   void* ch = nullptr;          // chord lengths: bit planes, histograms, result, events (chs_chords.hip), at the first look
   void* cmp = nullptr;         // composition: partial slots, histogram, select tables, result, events (chs_composition.hip), at the first look
+  void* tp = nullptr;          // two-point correlation: bit plane, pair counts, result, events (chs_two_point.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -468,3 +469,13 @@ int chs_cmp_select(Engine* E, hipStream_t s, void** buf, int32_t nq, const int64
 int chs_cmp_last_ms(const void* h, const void* buf, double* ms, const char* what);
 void chs_cmp_free(void** buf);
 void chs_cmp_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- two-point correlation (chs_two_point.hip) ---------------------------------
+// The pair counts of both phases of E's field thresholded at `threshold` for every displacement up to rmax (DESIGN.md
+// section 3i), on stream `s` with the buffer set *buf (the handle's own, or the batch's one set), allocated here at the
+// first look: out[CHS_TP_WORDS].  The count table of the last look of a buffer set: chs_tp_counts.
+int chs_tp_look(Engine* E, hipStream_t s, void** buf, double threshold, int32_t rmax, int64_t* out, const char* who);
+int chs_tp_counts(void* buf, int device, hipStream_t s, int64_t n, int64_t* out, const char* who);
+int chs_tp_last_ms(const void* h, const void* buf, double* ms, const char* what);
+void chs_tp_free(void** buf);
+void chs_tp_forget(void* buf);   // the buffers stay, the last look goes

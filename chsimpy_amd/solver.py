@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, composition, distance, morphology, mport, spectrum
+from . import _lib, chords, components, composition, distance, morphology, mport, spectrum, two_point
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -243,6 +243,24 @@ class Solver:
                 part = slice(int(k), int(k) + composition.CHS_CMP_MAX_RANKS)
                 found.update(zip(qs[part], (float(v) for v in eng.composition_select(ranks[part]))))
         return composition.Composition(iw, fw, self.params.N, t, hist=counts, quantiles=found, delx=self.solution.delx)
+
+    def two_point(self, threshold=None, rmax=two_point.DEFAULT_RMAX, counts=True):
+        """The two-point correlation of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): for either phase the number of pixel pairs of that phase at every displacement (dy, dx)
+        with ``0 <= dy <= rmax, |dx| <= rmax`` -- the two-point probability function S2 as a full map, its radial
+        average, the autocovariance and its first zero (the real-space domain size), the cross-phase correlation -- a
+        self-contained `two_point.TwoPoint` from one look on the device between two calls, which the run does not
+        notice.  ``rmax`` left at its default is clipped to ``two_point.max_r(N) = min(N - 1, 256)``; a value given
+        outside ``[1, max_r(N)]`` raises.  The count table (2 (rmax + 1)(2 rmax + 1) integers) is fetched in this call
+        unless ``counts=False``; nothing N x N leaves the device.  A field the host edited is pushed first, as
+        solve_or_resume does.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        N = self.params.N
+        r = min(int(rmax), two_point.max_r(N)) if rmax is two_point.DEFAULT_RMAX else rmax
+        r = two_point.check_rmax(N, r)
+        eng = self._look_engine()
+        words, c = eng.two_point_look(t, r, counts)
+        return two_point.TwoPoint(words, N, t, r, counts=c, delx=self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

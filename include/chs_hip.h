@@ -520,6 +520,50 @@ int chs_composition_last_ms(chs_handle h, double* ms);
  * D = log2(threads) + ceil(log2(max_groups)) deep. */
 int chs_composition_tile(int32_t* elems_per_thread, int32_t* threads, int32_t* max_groups, int32_t* digit_bits);
 
+/* ---- Two-point correlation: the pair counts of both phases at every displacement ----
+ * For the N x N field U, a finite threshold t and an integer rmax with 1 <= rmax <= chs_two_point_max_r(N), where
+ * chs_two_point_max_r(N) = min(N - 1, CHS_TP_MAX_R = 256), and 0 for N < 2:
+ * Phases: those of chs_chords.  Phase 0 is X[i][j] = ((double)U[i][j] < t); a NaN pixel and a pixel equal to t are not
+ * phase 0.  Phase 1 is the complement inside the grid.
+ * Displacements: (dy, dx) with 0 <= dy <= rmax and -rmax <= dx <= rmax.  The other half-plane is the mirror image
+ * (c(-dy, -dx) = c(dy, dx)) and is not stored.
+ * Pair count: c[p][dy][dx + rmax], int64, laid out as [2][rmax + 1][2 rmax + 1]: the number of positions (i, j) for which
+ * (i, j) and (i + dy, j + dx) are both inside the grid and both of phase p.  There is no wrap-around.  The window holds
+ * pairs(dy, dx) = (N - dy)(N - |dx|) positions.  chs_two_point_size(N, rmax) = 2 (rmax + 1)(2 rmax + 1), and 0 for
+ * arguments out of range.
+ * Summary: CHS_TP_WORDS = 8 int64 words.  N_BELOW, N_ABOVE: c[p][0][rmax], the pixels of the phase.  ADJ_ROWS_BELOW,
+ * ADJ_COLS_BELOW, ADJ_ROWS_ABOVE, ADJ_COLS_ABOVE: c[p] at (dy, dx) = (0, 1), the neighbours within a row, and at (1, 0),
+ * the neighbours within a column.  SUM_BELOW, SUM_ABOVE: the sum of all entries of c[p].
+ * Everything is an integer and every sum is order-free: two looks return the same bits.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone and writes buffers of its own (allocated at the first look, freed with the handle; a look with another rmax
+ * re-sizes the count table), so the run does not notice it.  The count table of the last look stays available until the
+ * next look.  The look checks itself: N_BELOW + N_ABOVE = N^2; the row dy = 0 of both tables is symmetric in dx;
+ * c[0] + c[1] <= pairs entry by entry and no entry is negative; a violation makes the look return CHS_ECHECK and
+ * chs_last_error names it.  CHS_EINVAL, the last look undisturbed, for a null argument, a threshold that is not finite,
+ * rmax out of range, N above 16384, or n != chs_two_point_size(N, rmax of the last look) on fetch (the message gives the
+ * expected value); CHS_ESTATE for _counts / _last_ms without a look. */
+#define CHS_TP_MAX_R 256
+#define CHS_TP_WORDS 8
+#define CHS_TP_N_BELOW 0
+#define CHS_TP_N_ABOVE 1
+#define CHS_TP_ADJ_ROWS_BELOW 2
+#define CHS_TP_ADJ_COLS_BELOW 3
+#define CHS_TP_ADJ_ROWS_ABOVE 4
+#define CHS_TP_ADJ_COLS_ABOVE 5
+#define CHS_TP_SUM_BELOW 6
+#define CHS_TP_SUM_ABOVE 7
+#define CHS_TP_CHUNK 2048 /* the pixels of a row that one workgroup of the pair kernel owns (chs_two_point_tile gives the rest) */
+int32_t chs_two_point_max_r(int32_t N);                 /* 0 for N < 2 */
+int64_t chs_two_point_size(int32_t N, int32_t rmax);    /* 0 for arguments out of range */
+int chs_two_point(chs_handle h, double threshold, int32_t rmax, int64_t out[CHS_TP_WORDS]);
+int chs_two_point_counts(chs_handle h, int64_t n, int64_t* out);   /* [2][rmax + 1][2 rmax + 1] of the last look */
+/* Device time (ms, HIP events) of the handle's last look, first launch to last. */
+int chs_two_point_last_ms(chs_handle h, double* ms);
+/* The kernels' geometry (what the tests size their fields by): the pixels of a row in one word, the rows of a band of
+ * the pair kernel, and the lanes of its workgroup; a workgroup owns band_rows rows of CHS_TP_CHUNK pixels. */
+int chs_two_point_tile(int32_t* word_bits, int32_t* band_rows, int32_t* lanes);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -617,6 +661,12 @@ int chs_batch_composition(chs_batch b, int32_t member, double threshold, int32_t
 int chs_batch_composition_hist(chs_batch b, int32_t nbins, int64_t* out);
 int chs_batch_composition_select(chs_batch b, int32_t member, int32_t nq, const int64_t* ranks, double* values);
 int chs_batch_composition_last_ms(chs_batch b, double* ms);
+/* chs_two_point of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of buffers for the batch,
+ * so the count table and the time are those of the batch's last look, whichever member it was.  Words and counts are those
+ * of the member's single handle on the same field.  The members' states, fields and records stay untouched. */
+int chs_batch_two_point(chs_batch b, int32_t member, double threshold, int32_t rmax, int64_t out[CHS_TP_WORDS]);
+int chs_batch_two_point_counts(chs_batch b, int64_t n, int64_t* out);
+int chs_batch_two_point_last_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }
