@@ -35,6 +35,9 @@ CHS_CMP_MAX_RANKS = 8         # ranks of one chs_composition_select
 CHS_TP_WORDS = 8              # int64 words of chs_two_point: n, the four neighbour counts and the table's sum per phase
 CHS_TP_MAX_R = 256            # rmax of chs_two_point at most
 CHS_TP_CHUNK = 2048           # the pixels of a row that one workgroup of its pair kernel owns
+CHS_CT_WORDS = 16             # int64 words of chs_contour (chsimpy_amd/contour.py names them)
+CHS_CT_SUMS = 6               # its float64 sums: txx, txy, tyy, k1, ka, k2
+CHS_CT_MAX_BINS = 1024        # bins of its curvature histogram at most
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -62,6 +65,8 @@ SYMBOLS = (
     'chs_batch_composition', 'chs_batch_composition_hist', 'chs_batch_composition_select', 'chs_batch_composition_last_ms',
     'chs_two_point_max_r', 'chs_two_point_size', 'chs_two_point', 'chs_two_point_counts', 'chs_two_point_last_ms',
     'chs_two_point_tile', 'chs_batch_two_point', 'chs_batch_two_point_counts', 'chs_batch_two_point_last_ms',
+    'chs_contour', 'chs_contour_hist', 'chs_contour_map', 'chs_contour_last_ms', 'chs_contour_tile',
+    'chs_batch_contour', 'chs_batch_contour_hist', 'chs_batch_contour_map', 'chs_batch_contour_last_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -233,6 +238,15 @@ def load():
     lib.chs_batch_two_point.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, i64p]
     lib.chs_batch_two_point_counts.argtypes = [vp, C.c_int64, i64p]
     lib.chs_batch_two_point_last_ms.argtypes = [vp, dp]
+    lib.chs_contour.argtypes = [vp, C.c_double, C.c_int32, C.c_double, C.c_int32, i64p, dp]
+    lib.chs_contour_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_contour_map.argtypes = [vp, C.c_int64, dp]
+    lib.chs_contour_last_ms.argtypes = [vp, dp]
+    lib.chs_contour_tile.argtypes = [i32p, i32p, i32p, i32p]
+    lib.chs_batch_contour.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, i64p, dp]
+    lib.chs_batch_contour_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_batch_contour_map.argtypes = [vp, C.c_int64, dp]
+    lib.chs_batch_contour_last_ms.argtypes = [vp, dp]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -339,6 +353,25 @@ def composition_sum_terms(N, tile=None):
     tiles = -(-(N * N) // (threads * ept))
     groups = min(tiles, max_groups)
     return ept * -(-tiles // groups), (threads - 1).bit_length() + (max_groups - 1).bit_length()
+
+
+def contour_tile():
+    """(tile_w, tile_h, threads, fin_threads) of the kernels of chs_contour (chs_contour_tile): a workgroup of `threads`
+    threads owns tile_w x tile_h cells, and the finishing workgroup has fin_threads threads."""
+    v = [C.c_int32(0) for _ in range(4)]
+    rc = load().chs_contour_tile(*(C.byref(x) for x in v))
+    if rc != CHS_OK:
+        raise EngineError(f"chs_contour_tile failed ({rc})")
+    return tuple(int(x.value) for x in v)
+
+
+def contour_sum_terms(N, tile=None):
+    """(E, D) of the error bound of the float sums of chs_contour at grid size N: the terms that are
+    added one after the other -- a thread's at most two segments of each of its queue entries, then the slots of a thread
+    of the finishing workgroup, the first of which is the end of the first chain -- and the depth of the two trees."""
+    tw, th, threads, fin = tile or contour_tile()
+    tiles = -(-(N - 1) // tw) * -(-(N - 1) // th)
+    return 2 * (tw * th // threads) + -(-tiles // fin) - 1, (threads - 1).bit_length() + (fin - 1).bit_length()
 
 
 def __getattr__(name):
@@ -536,6 +569,39 @@ class _Looks:
     def two_point_tile():
         return two_point_tile()
 
+    _ct_bins = 0
+
+    def _contour(self, lead, threshold, bins, kmax, map=False):
+        words, sums = np.empty(CHS_CT_WORDS, dtype=np.int64), np.empty(CHS_CT_SUMS, dtype=np.float64)
+        self._look_call('contour', *lead, float(threshold), int(bins), float(kmax), 1 if map else 0, _i64ptr(words), _dptr(sums))
+        self._ct_bins = int(bins)
+        return words, sums
+
+    def contour_hist(self, bins=None):
+        """int64 [2][bins] of the last look: the curvature cells per bin, then their fix(ell) per bin (bins: that of the
+        last look of this object)."""
+        out = np.empty((2, self._ct_bins if bins is None else int(bins)), dtype=np.int64)
+        self._look_call('contour_hist', out.shape[1], _i64ptr(out))
+        return out
+
+    def contour_map(self):
+        """float64 [2][N-1][N-1] of the last look, if it was taken with the map: ell per cell, then kappa per cell."""
+        out = np.empty((2, self.N - 1, self.N - 1), dtype=np.float64)
+        self._look_call('contour_map', out.size, _dptr(out))
+        return out
+
+    def _contour_look(self, lead, threshold, bins, kmax, hist, map):
+        words, sums = self._contour(lead, threshold, bins, kmax, map)
+        return words, sums, (self.contour_hist() if hist else None), (self.contour_map() if map else None)
+
+    def contour_ms(self):
+        """Device time (ms) of the last `contour`."""
+        return self._last_ms(self._prefix + 'contour_last_ms')
+
+    @staticmethod
+    def contour_tile():
+        return contour_tile()
+
     @staticmethod
     def two_point_max_r(N):
         return two_point_max_r(N)
@@ -716,6 +782,15 @@ class Engine(_Looks):
     def two_point_look(self, threshold, rmax, counts=True):
         """One look with what belongs to it: (words, count table or None)."""
         return self._two_point_look((), threshold, rmax, counts)
+
+    def contour(self, threshold, bins=64, kmax=1.0, map=False):
+        """The 16 int64 words and the 6 float64 sums of the contour of the field the device holds (chs_contour;
+        chsimpy_amd/contour.py names them).  The histograms and the map of this look: `contour_hist`, `contour_map`."""
+        return self._contour((), threshold, bins, kmax, map)
+
+    def contour_look(self, threshold, bins=64, kmax=1.0, hist=True, map=False):
+        """One look with what belongs to it: (words, sums, histograms or None, map or None)."""
+        return self._contour_look((), threshold, bins, kmax, hist, map)
 
     def morphology_ms(self):
         """Device time (ms) of the last `morphology`."""
@@ -906,6 +981,13 @@ class Batch(_Looks):
 
     def two_point_look(self, member, threshold, rmax, counts=True):
         return self._two_point_look((int(member),), threshold, rmax, counts)
+
+    def contour(self, member, threshold, bins=64, kmax=1.0, map=False):
+        """`Engine.contour` of one member (chs_batch_contour)."""
+        return self._contour((int(member),), threshold, bins, kmax, map)
+
+    def contour_look(self, member, threshold, bins=64, kmax=1.0, hist=True, map=False):
+        return self._contour_look((int(member),), threshold, bins, kmax, hist, map)
 
     def get_state(self, member):
         s = chs_state()

@@ -34,7 +34,7 @@ import functools
 
 import numpy as np
 
-from . import _lib, two_point
+from . import _lib, contour, two_point
 from .solver import Solver
 
 
@@ -127,7 +127,7 @@ class _Member:
         return self._b.morphology(threshold, self._m)
 
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
-              'composition_look', 'composition_select', 'two_point', 'two_point_look')
+              'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -317,6 +317,10 @@ class BatchSolver:
     def two_point(self, member=None, threshold=None, rmax=two_point.DEFAULT_RMAX, counts=True):
         """The members' two-point correlations (`Solver.two_point`), a `two_point.TwoPoint` each: _member_by_member."""
         return self._member_by_member('two_point', member, threshold, rmax, counts)
+
+    def contour(self, member=None, threshold=None, bins=contour.DEFAULT_BINS, kmax=contour.DEFAULT_KMAX, hist=True, map=False):
+        """The members' sub-pixel interfaces (`Solver.contour`), a `contour.Contour` each: _member_by_member."""
+        return self._member_by_member('contour', member, threshold, bins, kmax, hist, map)
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

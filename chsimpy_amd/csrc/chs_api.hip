@@ -92,6 +92,7 @@ static void free_engine(Engine* E) {
   chs_ch_free(&E->ch);
   chs_cmp_free(&E->cmp);
   chs_tp_free(&E->tp);
+  chs_ct_free(&E->ct);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
   hipFree(E->dT1); hipFree(E->dHat);
   if (E->dHat2) hipFree(E->dHat2);
@@ -197,6 +198,7 @@ static int rearm(Engine* E, const chs_consts* c) {
   chs_ch_forget(E->ch);
   chs_cmp_forget(E->cmp);
   chs_tp_forget(E->tp);
+  chs_ct_forget(E->ct);
   read_env_hooks(E);
   if (E->engine == CHS_ENGINE_FAST) return chs_fast_rearm(E);
   return CHS_OK;

@@ -167,6 +167,7 @@ struct Batch {
   void* ch = nullptr;            // chs_batch_chords: the batch's one set of buffers (chs_chords.hip), at the first look
   void* cmp = nullptr;           // chs_batch_composition: the batch's one set of buffers (chs_composition.hip), at the first look
   void* tp = nullptr;            // chs_batch_two_point: the batch's one set of buffers (chs_two_point.hip), at the first look
+  void* ct = nullptr;            // chs_batch_contour: the batch's one set of buffers (chs_contour.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -189,6 +190,7 @@ void batch_free(Batch* b) {
   chs_ch_free(&b->ch);
   chs_cmp_free(&b->cmp);
   chs_tp_free(&b->tp);
+  chs_ct_free(&b->ct);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -910,4 +912,30 @@ extern "C" int chs_batch_two_point_counts(chs_batch h, int64_t n, int64_t* out) 
 extern "C" int chs_batch_two_point_last_ms(chs_batch h, double* ms) {
   Batch* b = as_batch(h);
   return chs_tp_last_ms(b, b ? b->tp : nullptr, ms, "chs_batch_two_point");
+}
+
+// The contour of one member: the single handle's look on the batch's stream, with the batch's one set of buffers.
+extern "C" int chs_batch_contour(chs_batch h, int32_t member, double threshold, int32_t bins, double kmax, int32_t want_map,
+                                 int64_t* words, double* sums) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_contour: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_contour: no such member");
+  return chs_ct_look(b->m[(size_t)member], b->stream, &b->ct, threshold, bins, kmax, want_map, words, sums, "chs_batch_contour");
+}
+
+extern "C" int chs_batch_contour_hist(chs_batch h, int32_t bins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_contour_hist: null handle");
+  return chs_ct_hist(b->ct, b->m[0]->hc.device, b->stream, bins, out, "chs_batch_contour_hist");
+}
+
+extern "C" int chs_batch_contour_map(chs_batch h, int64_t n, double* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_contour_map: null handle");
+  return chs_ct_map(b->ct, b->m[0]->hc.device, b->stream, n, out, "chs_batch_contour_map");
+}
+
+extern "C" int chs_batch_contour_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_ct_last_ms(b, b ? b->ct : nullptr, ms, "chs_batch_contour");
 }

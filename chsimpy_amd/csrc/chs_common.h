@@ -263,6 +263,7 @@ struct Engine {
   void* ch = nullptr;          // chord lengths: bit planes, histograms, result, events (chs_chords.hip), at the first look
   void* cmp = nullptr;         // composition: partial slots, histogram, select tables, result, events (chs_composition.hip), at the first look
   void* tp = nullptr;          // two-point correlation: bit plane, pair counts, result, events (chs_two_point.hip), at the first look
+  void* ct = nullptr;          // contour: slots, histograms, map, result, events (chs_contour.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -479,3 +480,15 @@ int chs_tp_counts(void* buf, int device, hipStream_t s, int64_t n, int64_t* out,
 int chs_tp_last_ms(const void* h, const void* buf, double* ms, const char* what);
 void chs_tp_free(void** buf);
 void chs_tp_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- contour (chs_contour.hip) -------------------------------------------------
+// Length, orientation tensor and curvature of the level set U = threshold of E's field on stream
+// `s` with the buffer set *buf (the handle's own, or the batch's one set), allocated here at the first look:
+// words[CHS_CT_WORDS], sums[CHS_CT_SUMS].  Histograms and map of the last look of a buffer set: chs_ct_hist, chs_ct_map.
+int chs_ct_look(Engine* E, hipStream_t s, void** buf, double threshold, int32_t bins, double kmax, int32_t want_map,
+                int64_t* words, double* sums, const char* who);
+int chs_ct_hist(void* buf, int device, hipStream_t s, int32_t bins, int64_t* out, const char* who);
+int chs_ct_map(void* buf, int device, hipStream_t s, int64_t n, double* out, const char* who);
+int chs_ct_last_ms(const void* h, const void* buf, double* ms, const char* what);
+void chs_ct_free(void** buf);
+void chs_ct_forget(void* buf);   // the buffers stay, the last look goes

@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, composition, distance, morphology, mport, spectrum, two_point
+from . import _lib, chords, components, composition, contour, distance, morphology, mport, spectrum, two_point
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -261,6 +261,22 @@ class Solver:
         eng = self._look_engine()
         words, c = eng.two_point_look(t, r, counts)
         return two_point.TwoPoint(words, N, t, r, counts=c, delx=self.solution.delx)
+
+    def contour(self, threshold=None, bins=contour.DEFAULT_BINS, kmax=contour.DEFAULT_KMAX, hist=True, map=False):
+        """The interface of the field the device holds below the pixel: the marching-squares contour of ``U =
+        threshold`` (None: ``params.threshold``) -- its true length per area ``S_V`` (the pixel perimeter of
+        `morphology` overestimates an isotropic interface by 4 / pi), its orientation tensor, and the curvature of the
+        level set at every crossed cell from the field's own derivatives: mean, mean absolute and rms curvature, the
+        integral of kappa^2 and a histogram of ``bins`` bins over ``[-kmax, kmax]`` (1 / pixel) by cells and by length --
+        a self-contained `contour.Contour` from one sweep on the device between two calls, which the run does not
+        notice.  The histograms are fetched in this call unless ``hist=False``; the two (N-1) x (N-1) maps of ell and
+        kappa only with ``map=True`` (without it nothing N x N leaves the device).  A field the host edited is pushed
+        first, as solve_or_resume does.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        nb, km = contour.check_bins(bins), contour.check_kmax(kmax)
+        eng = self._look_engine()
+        words, sums, hi, mp = eng.contour_look(t, nb, km, hist, map)
+        return contour.Contour(words, sums, self.params.N, t, nb, km, hist=hi, map=mp, delx=self.solution.delx)
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

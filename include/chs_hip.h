@@ -564,6 +564,91 @@ int chs_two_point_last_ms(chs_handle h, double* ms);
  * the pair kernel, and the lanes of its workgroup; a workgroup owns band_rows rows of CHS_TP_CHUNK pixels. */
 int chs_two_point_tile(int32_t* word_bits, int32_t* band_rows, int32_t* lanes);
 
+/* ---- Sub-pixel interface: contour length, orientation and curvature of the level set U = t ----
+ * Setting.  The N x N field U[i][j], i the row (y) and j the column (x), N >= 2; every value widened to double; a finite
+ * threshold t.  A pixel is below when (double)U < t -- phase 0 of chs_chords: a NaN and a pixel equal to t are not below.
+ * Cell (i, j), 0 <= i, j <= N - 2, has the corners a = U[i][j], b = U[i][j+1], c = U[i+1][j], d = U[i+1][j+1] and the
+ * code below(a) + 2 below(b) + 4 below(c) + 8 below(d).
+ * Vertices.  One on every grid edge whose two pixels p and q (p the one with the lower index) are unlike: lo the below
+ * value, hi the other, s = (t - lo) / (hi - lo), s = 0.5 if either value is not finite; the vertex lies at the fraction s
+ * from p if p is below and at 1 - s otherwise.  In cell coordinates a cell's vertices are T = (x_T, 0), B = (x_B, 1),
+ * L = (0, y_L), R = (1, y_R).
+ * Segments, from the first vertex to the second: codes 1, 14: L-T; 2, 13: T-R; 4, 11: L-B; 8, 7: B-R; 3, 12: L-R;
+ * 5, 10: T-B; 6 (a saddle): T-R and L-B; 9 (a saddle): L-T and B-R -- in a saddle every below corner is cut off on its
+ * own, the below phase being 4-connected as for the Euler number euler4.  For a segment from P to Q, every operation
+ * rounded on its own: dx = Q.x - P.x, dy = Q.y - P.y, l = sqrt(dx dx + dy dy); txx = dx dx / l, txy = dx dy / l,
+ * tyy = dy dy / l, each 0 where l == 0.  A cell's ell is the sum of its l, at most two terms in the order above.
+ * Curvature, for a crossed cell that is no saddle and has 1 <= i, j <= N - 3, with A(di, dj) = U[i+di][j+dj]:
+ *   ux  = ((A(0,1) + A(1,1)) - (A(0,0) + A(1,0))) 0.5,   uy = ((A(1,0) + A(1,1)) - (A(0,0) + A(0,1))) 0.5
+ *   uxy = (A(1,1) - A(1,0)) - (A(0,1) - A(0,0))
+ *   uxx = (((A(0,2) - A(0,1)) - (A(0,0) - A(0,-1))) + ((A(1,2) - A(1,1)) - (A(1,0) - A(1,-1)))) 0.25
+ *   uyy = (((A(2,0) - A(1,0)) - (A(0,0) - A(-1,0))) + ((A(2,1) - A(1,1)) - (A(0,1) - A(-1,1)))) 0.25
+ *   g2  = ux ux + uy uy,   kappa = ((uxx (uy uy) - (2 (ux uy)) uxy) + uyy (ux ux)) / (g2 sqrt(g2))
+ * the divergence of grad U / |grad U|: positive where the below phase is convex, in 1 / pixel.  A crossed cell that is no
+ * saddle and lacks the full stencil is a wall cell; one whose 16 stencil values are not all finite or whose kappa is not
+ * finite is a bad cell.  Wall cells, bad cells and saddles take no part in the curvature results; they are counted.
+ * Fixed point: fix(x) = (int64)(x 2^30), truncated; lengths are summed as fix(ell), order-free.
+ * words, CHS_CT_WORDS int64: CELLS_ONE (one or three below corners), CELLS_TWO (codes 3, 5, 10, 12), SADDLES,
+ *   VERTICES_ROWS and VERTICES_COLS (unlike neighbours within a row, within a column), ENDS (vertices on the four
+ *   outermost grid lines), SEGMENTS, CELLS_CURV, CELLS_WALL, CELLS_BAD, L_FIX (fix(ell) over all cells), L_CURV_FIX (over
+ *   the curvature cells), HIST_UNDER, HIST_OVER, N_BELOW, N_NONFINITE (the pixels that are NaN or infinite).
+ * sums, CHS_CT_SUMS doubles: TXX, TXY, TYY over all segments; K1 = sum ell kappa, KA = sum ell |kappa|, K2 = sum ell
+ *   (kappa kappa) over the curvature cells.  They are bit for bit the same from look to look: the crossed cells of a
+ *   workgroup's tile are queued in row-major order, thread q adds the queue's entries q, q + threads, ... in that order,
+ *   the workgroup joins its threads by a fixed tree into a slot of its own and one workgroup joins the slots, each of its
+ *   threads every fin_threads-th slot in order and then a fixed tree; no float atomics.
+ * The histogram, for 1 <= bins <= CHS_CT_MAX_BINS and a finite kmax > 0, with SCALE = bins / (2 kmax) in double: a
+ *   curvature cell with kappa in [-kmax, kmax] is in bin min(bins - 1, (int64)((kappa + kmax) SCALE)); kappa < -kmax is
+ *   counted by HIST_UNDER, kappa > kmax by HIST_OVER.  int64 [2][bins]: the cells per bin, then their fix(ell) per bin.
+ * The map, if want_map != 0: double [2][N-1][N-1]: ell per cell, 0 where the cell is not crossed; then kappa per cell,
+ *   NaN where the cell is not a curvature cell.  It exists until the next look; a look without want_map frees it.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone and writes buffers of its own, so the run does not notice it.  The look checks itself: SEGMENTS = CELLS_ONE +
+ * CELLS_TWO + 2 SADDLES; 2 SEGMENTS = 2 (VERTICES_ROWS + VERTICES_COLS) - ENDS; CELLS_CURV + CELLS_WALL + CELLS_BAD =
+ * CELLS_ONE + CELLS_TWO; the histogram's cells + HIST_UNDER + HIST_OVER = CELLS_CURV; the histogram's lengths add up to
+ * L_CURV_FIX at most, and to it when HIST_UNDER + HIST_OVER = 0; |TXX + TYY - L_FIX / 2^30| is within the sums' error
+ * bound plus SEGMENTS 2^-30 (skipped where the sums are not finite); a violation is CHS_ECHECK and chs_last_error names
+ * it.  CHS_EINVAL, the last look undisturbed: a null argument, a threshold or kmax that is not finite, kmax <= 0, bins
+ * outside [1, CHS_CT_MAX_BINS], N < 2 or above 16384, a fetch with another size than the look's (the message gives the
+ * expected value).  CHS_ESTATE for a fetch or _last_ms without a look, for _map after a look without want_map. */
+#define CHS_CT_MAX_BINS 1024
+#define CHS_CT_WORDS 16
+#define CHS_CT_CELLS_ONE 0
+#define CHS_CT_CELLS_TWO 1
+#define CHS_CT_SADDLES 2
+#define CHS_CT_VERTICES_ROWS 3
+#define CHS_CT_VERTICES_COLS 4
+#define CHS_CT_ENDS 5
+#define CHS_CT_SEGMENTS 6
+#define CHS_CT_CELLS_CURV 7
+#define CHS_CT_CELLS_WALL 8
+#define CHS_CT_CELLS_BAD 9
+#define CHS_CT_L_FIX 10
+#define CHS_CT_L_CURV_FIX 11
+#define CHS_CT_HIST_UNDER 12
+#define CHS_CT_HIST_OVER 13
+#define CHS_CT_N_BELOW 14
+#define CHS_CT_N_NONFINITE 15
+#define CHS_CT_SUMS 6
+#define CHS_CT_TXX 0
+#define CHS_CT_TXY 1
+#define CHS_CT_TYY 2
+#define CHS_CT_K1 3
+#define CHS_CT_KA 4
+#define CHS_CT_K2 5
+#define CHS_CT_FIX_BITS 30
+int chs_contour(chs_handle h, double threshold, int32_t bins, double kmax, int32_t want_map, int64_t words[CHS_CT_WORDS],
+                double sums[CHS_CT_SUMS]);
+int chs_contour_hist(chs_handle h, int32_t bins, int64_t* out);   /* [2][bins] of the last look */
+int chs_contour_map(chs_handle h, int64_t n, double* out);        /* n = 2 (N-1)^2: [2][N-1][N-1] of the last look */
+/* Device time (ms, HIP events) of the handle's last look, first launch to last. */
+int chs_contour_last_ms(chs_handle h, double* ms);
+/* The kernels' geometry (what the tests size their fields by, and the operands of the sums' error bound): a workgroup of
+ * `threads` threads owns tile_w x tile_h cells; a thread adds at most 2 tile_w tile_h / threads terms one after the other,
+ * a thread of the finishing workgroup ceil(tiles / fin_threads) slots, tiles = ceil((N-1) / tile_w) ceil((N-1) / tile_h);
+ * the trees above them are log2(threads) and log2(fin_threads) deep. */
+int chs_contour_tile(int32_t* tile_w, int32_t* tile_h, int32_t* threads, int32_t* fin_threads);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -667,6 +752,15 @@ int chs_batch_composition_last_ms(chs_batch b, double* ms);
 int chs_batch_two_point(chs_batch b, int32_t member, double threshold, int32_t rmax, int64_t out[CHS_TP_WORDS]);
 int chs_batch_two_point_counts(chs_batch b, int64_t n, int64_t* out);
 int chs_batch_two_point_last_ms(chs_batch b, double* ms);
+/* chs_contour of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of buffers for the batch,
+ * so the histogram, the map and the time are those of the batch's last look, whichever member it was.  Words, sums,
+ * histogram and map are those of the member's single handle on the same field, bit for bit.  The members' states, fields
+ * and records stay untouched. */
+int chs_batch_contour(chs_batch b, int32_t member, double threshold, int32_t bins, double kmax, int32_t want_map,
+                      int64_t words[CHS_CT_WORDS], double sums[CHS_CT_SUMS]);
+int chs_batch_contour_hist(chs_batch b, int32_t bins, int64_t* out);
+int chs_batch_contour_map(chs_batch b, int64_t n, double* out);
+int chs_batch_contour_last_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }
