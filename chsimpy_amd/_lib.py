@@ -38,6 +38,8 @@ CHS_TP_CHUNK = 2048           # the pixels of a row that one workgroup of its pa
 CHS_CT_WORDS = 16             # int64 words of chs_contour (chsimpy_amd/contour.py names them)
 CHS_CT_SUMS = 6               # its float64 sums: txx, txy, tyy, k1, ka, k2
 CHS_CT_MAX_BINS = 1024        # bins of its curvature histogram at most
+CHS_SH_WORDS = 17             # int64 words of chs_shapes (chsimpy_amd/shapes.py names them)
+CHS_SH_COLS = 16              # int64 columns of its table
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -67,6 +69,7 @@ SYMBOLS = (
     'chs_two_point_tile', 'chs_batch_two_point', 'chs_batch_two_point_counts', 'chs_batch_two_point_last_ms',
     'chs_contour', 'chs_contour_hist', 'chs_contour_map', 'chs_contour_last_ms', 'chs_contour_tile',
     'chs_batch_contour', 'chs_batch_contour_hist', 'chs_batch_contour_map', 'chs_batch_contour_last_ms',
+    'chs_shapes', 'chs_shapes_table', 'chs_shapes_last_ms', 'chs_batch_shapes', 'chs_batch_shapes_table',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -247,6 +250,11 @@ def load():
     lib.chs_batch_contour_hist.argtypes = [vp, C.c_int32, i64p]
     lib.chs_batch_contour_map.argtypes = [vp, C.c_int64, dp]
     lib.chs_batch_contour_last_ms.argtypes = [vp, dp]
+    lib.chs_shapes.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, i64p]
+    lib.chs_shapes_table.argtypes = [vp, C.c_int64, i64p]
+    lib.chs_shapes_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_shapes.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, i64p]
+    lib.chs_batch_shapes_table.argtypes = [vp, C.c_int64, i64p]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -602,6 +610,24 @@ class _Looks:
     def contour_tile():
         return contour_tile()
 
+    _sh_count = 0
+
+    def _shapes(self, lead, threshold, connectivity, side):
+        out = np.empty(CHS_SH_WORDS, dtype=np.int64)
+        self._look_call('shapes', *lead, float(threshold), int(connectivity), int(side), _i64ptr(out))
+        self._sh_count = self._cc_count = int(out[0])      # (a shapes look is a components look too)
+        return out
+
+    def shapes_table(self):
+        """int64 [count][16] of the last shapes look (chsimpy_amd/shapes.py names the columns)."""
+        out = np.empty((self._sh_count, CHS_SH_COLS), dtype=np.int64)
+        self._look_call('shapes_table', self._sh_count, _i64ptr(out))
+        return out
+
+    def _shapes_look(self, lead, threshold, connectivity, side, labels):
+        words = self._shapes(lead, threshold, connectivity, side)
+        return words, self.shapes_table(), self.components_table(), (self.components_labels() if labels else None)
+
     @staticmethod
     def two_point_max_r(N):
         return two_point_max_r(N)
@@ -791,6 +817,19 @@ class Engine(_Looks):
     def contour_look(self, threshold, bins=64, kmax=1.0, hist=True, map=False):
         """One look with what belongs to it: (words, sums, histograms or None, map or None)."""
         return self._contour_look((), threshold, bins, kmax, hist, map)
+
+    def shapes(self, threshold, connectivity=4, side=CHS_CC_BELOW):
+        """The 17 int64 summary words of the droplet shapes of the field the device holds (chs_shapes;
+        chsimpy_amd/shapes.py names them).  The table of this look: `shapes_table`; it is a components look as well."""
+        return self._shapes((), threshold, connectivity, side)
+
+    def shapes_look(self, threshold, connectivity, side, labels=False):
+        """One look with what belongs to it: (words, shape table, component table, labels or None)."""
+        return self._shapes_look((), threshold, connectivity, side, labels)
+
+    def shapes_ms(self):
+        """Device time (ms) of the sweep and the summary of the last `shapes`."""
+        return self._last_ms('chs_shapes_last_ms')
 
     def morphology_ms(self):
         """Device time (ms) of the last `morphology`."""
@@ -988,6 +1027,13 @@ class Batch(_Looks):
 
     def contour_look(self, member, threshold, bins=64, kmax=1.0, hist=True, map=False):
         return self._contour_look((int(member),), threshold, bins, kmax, hist, map)
+
+    def shapes(self, member, threshold, connectivity=4, side=CHS_CC_BELOW):
+        """`Engine.shapes` of one member (chs_batch_shapes)."""
+        return self._shapes((int(member),), threshold, connectivity, side)
+
+    def shapes_look(self, member, threshold, connectivity, side, labels=False):
+        return self._shapes_look((int(member),), threshold, connectivity, side, labels)
 
     def get_state(self, member):
         s = chs_state()

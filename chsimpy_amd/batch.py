@@ -127,7 +127,8 @@ class _Member:
         return self._b.morphology(threshold, self._m)
 
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
-              'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look')
+              'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look', 'shapes',
+              'shapes_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -321,6 +322,10 @@ class BatchSolver:
     def contour(self, member=None, threshold=None, bins=contour.DEFAULT_BINS, kmax=contour.DEFAULT_KMAX, hist=True, map=False):
         """The members' sub-pixel interfaces (`Solver.contour`), a `contour.Contour` each: _member_by_member."""
         return self._member_by_member('contour', member, threshold, bins, kmax, hist, map)
+
+    def shapes(self, member=None, threshold=None, connectivity=4, side='below', labels=False):
+        """The members' droplet shapes (`Solver.shapes`), a `shapes.Shapes` each: _member_by_member."""
+        return self._member_by_member('shapes', member, threshold, connectivity, side, labels)
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

@@ -168,6 +168,7 @@ struct Batch {
   void* cmp = nullptr;           // chs_batch_composition: the batch's one set of buffers (chs_composition.hip), at the first look
   void* tp = nullptr;            // chs_batch_two_point: the batch's one set of buffers (chs_two_point.hip), at the first look
   void* ct = nullptr;            // chs_batch_contour: the batch's one set of buffers (chs_contour.hip), at the first look
+  void* sh = nullptr;            // chs_batch_shapes: the batch's one set of buffers (chs_shapes.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -191,6 +192,7 @@ void batch_free(Batch* b) {
   chs_cmp_free(&b->cmp);
   chs_tp_free(&b->tp);
   chs_ct_free(&b->ct);
+  chs_sh_free(&b->sh);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -938,4 +940,20 @@ extern "C" int chs_batch_contour_map(chs_batch h, int64_t n, double* out) {
 extern "C" int chs_batch_contour_last_ms(chs_batch h, double* ms) {
   Batch* b = as_batch(h);
   return chs_ct_last_ms(b, b ? b->ct : nullptr, ms, "chs_batch_contour");
+}
+
+// The droplet shapes of one member: the single handle's look on the batch's stream, with the batch's one set of component
+// buffers and one set of shape buffers.
+extern "C" int chs_batch_shapes(chs_batch h, int32_t member, double threshold, int32_t connectivity, int32_t side,
+                                int64_t out[CHS_SH_WORDS]) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_shapes: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_shapes: no such member");
+  return chs_sh_look(b->m[(size_t)member], b->stream, &b->cc, &b->sh, threshold, connectivity, side, out, "chs_batch_shapes");
+}
+
+extern "C" int chs_batch_shapes_table(chs_batch h, int64_t rows, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_shapes_table: null handle");
+  return chs_sh_table(b->sh, b->m[0]->hc.device, b->stream, rows, out, "chs_batch_shapes_table");
 }

@@ -264,6 +264,7 @@ struct Engine {
   void* cmp = nullptr;         // composition: partial slots, histogram, select tables, result, events (chs_composition.hip), at the first look
   void* tp = nullptr;          // two-point correlation: bit plane, pair counts, result, events (chs_two_point.hip), at the first look
   void* ct = nullptr;          // contour: slots, histograms, map, result, events (chs_contour.hip), at the first look
+  void* sh = nullptr;          // droplet shapes: table, result, events (chs_shapes.hip), at the first look
   DevState* dState = nullptr;
   double* dRows = nullptr;     // timedata rows of the running call
   long long rowsCap = 0;
@@ -438,6 +439,26 @@ int chs_cc_table(void* buf, int device, hipStream_t s, int64_t rows, int32_t* ou
 int chs_cc_labels(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
 void chs_cc_free(void** buf);
 void chs_cc_forget(void* buf);   // the buffers stay, the last look goes
+// What the last look of a buffer set left on the device, for a look that builds on it (chs_shapes.hip): the root label of
+// every pixel, the number at every root, the table and its row count.  Read-only; CHS_ESTATE without a look.
+struct ChsCcSnapshot {
+  const int* L = nullptr;       // [N * N] the root's linear index, -1 for background
+  const int* id = nullptr;      // [N * N] at a root: its component number
+  const int* table = nullptr;   // [count][CHS_CC_COLS]
+  int64_t count = 0;
+};
+int chs_cc_snapshot(const void* buf, ChsCcSnapshot* out, const char* who);
+
+// ---- droplet shapes (chs_shapes.hip) -------------------------------------------
+// The shape table of E's field thresholded at `threshold` on stream `s`: a components look with
+// the buffer set *ccbuf first (it stays that look's snapshot), then the sweep with the buffer set *buf, both allocated
+// here at the first look: out[CHS_SH_WORDS].  The table of the last look of a buffer set: chs_sh_table.
+int chs_sh_look(Engine* E, hipStream_t s, void** ccbuf, void** buf, double threshold, int32_t connectivity, int32_t side,
+                int64_t* out, const char* who);
+int chs_sh_table(void* buf, int device, hipStream_t s, int64_t rows, int64_t* out, const char* who);
+int chs_sh_last_ms(const void* h, const void* buf, double* ms, const char* what);
+void chs_sh_free(void** buf);
+void chs_sh_forget(void* buf);   // the buffers stay, the last look goes
 
 // ---- distance transform (chs_distance.hip) -----------------------------------
 // The squared distances of E's field thresholded at `threshold` on stream `s` with the buffer set

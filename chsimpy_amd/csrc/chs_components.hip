@@ -516,6 +516,13 @@ void chs_cc_forget(void* buf) {
   s->labelled = false; s->count = 0;
 }
 
+int chs_cc_snapshot(const void* buf, ChsCcSnapshot* out, const char* who_) {
+  const CcBuf* s = (const CcBuf*)buf;
+  if (!s || !s->have) { chs_set_error(std::string(who_) + ": no components look to build on"); return CHS_ESTATE; }
+  out->L = s->L; out->id = s->id; out->table = s->table; out->count = s->count;
+  return CHS_OK;
+}
+
 int chs_cc_look(Engine* E, hipStream_t st, void** buf, double threshold, int32_t connectivity, int32_t side, int64_t* out,
                 const char* who_) {
   const std::string who(who_);

@@ -649,6 +649,75 @@ int chs_contour_last_ms(chs_handle h, double* ms);
  * the trees above them are log2(threads) and log2(fin_threads) deep. */
 int chs_contour_tile(int32_t* tile_w, int32_t* tile_h, int32_t* threads, int32_t* fin_threads);
 
+/* ---- Droplet shapes: moments, perimeter, holes and composition of every component -----------
+ * The foreground X, the connectivity (4 or 8), the side, the components and their numbering by ascending `first` are
+ * exactly those of chs_components.  A shapes look labels the field itself, by running the phases of chs_components on the
+ * handle's component buffers: a shapes look IS ALSO a components look of the same (threshold, connectivity, side), and
+ * afterwards chs_components_table and chs_components_labels return that labelling.  One more sweep over the field, the
+ * labels and the numbers then fills a table of its own, int64 [C][CHS_SH_COLS], one row per component k, which stays valid
+ * until the next shapes look on the handle (a later chs_components does not touch it).
+ * Pixel (i, j) has p = i N + j and x = (double)U[i][j].  Columns:
+ *   FIRST      that of the component table
+ *   AREA       pixels of k
+ *   PAIRS_H    pixels (i, j) of k whose right neighbour (i, j+1) is foreground
+ *   PAIRS_V    pixels (i, j) of k whose lower neighbour (i+1, j) is foreground
+ *   PAIRS_D    connectivity 8 only, otherwise 0: the diagonal foreground pairs {(i,j), (i+1,j+1)} and {(i,j+1), (i+1,j)},
+ *              each counted for the component of its upper pixel
+ *   TRIPLES    connectivity 8 only, otherwise 0: the 2 x 2 cells with exactly three foreground pixels, counted for the
+ *              component of the cell's first foreground pixel in the order a = (i,j), b = (i,j+1), c = (i+1,j),
+ *              d = (i+1,j+1)
+ *   QUADS      the 2 x 2 cells with four foreground pixels, counted for the component of the cell's upper left pixel
+ *   WALL       unit pixel edges of k that lie on the grid's boundary (a corner pixel has two)
+ *   SI, SJ, SII, SJJ, SIJ   the sums of i, j, i^2, j^2, i j over the pixels of k
+ *   SU_FIX     the sum of fix(x) over the pixels of k with fabs(x) <= 4.0
+ *   SUU_FIX    the sum of fix(x x) over the same pixels, the product rounded once in double
+ *   N_OUTSIDE  pixels of k with !(fabs(x) <= 4.0): NaN, infinite, or far outside the physical range
+ * fix(y) = (int64)(y 2^30), truncated (CHS_CT_FIX_BITS).  All pixels of a pair or a cell that is counted belong to one
+ * component under the connectivity it is counted for; the "counted for" rules only make the owner unique.  With
+ * N <= 16384 no sum reaches 2^63: SII, SJJ, SIJ stay below 2^28 2^28 = 2^56, SUU_FIX below 2^28 2^34 = 2^62.  Every cell is
+ * an integer and every accumulation an integer add, so the table does not depend on the order the device worked in: it is
+ * the numpy model's (chsimpy_amd/shapes.py) bit for bit, for both element types.
+ * Summary, CHS_SH_WORDS int64: the seven words of chs_components; the column sums of AREA, PAIRS_H, PAIRS_V, PAIRS_D,
+ * TRIPLES, QUADS, WALL, N_OUTSIDE; HOLES = the sum over k of 1 - euler_k, with euler_k = AREA - PAIRS_H - PAIRS_V + QUADS at
+ * connectivity 4 and AREA - PAIRS_H - PAIRS_V - PAIRS_D + TRIPLES + 3 QUADS at connectivity 8 (1 - euler_k: the holes of the
+ * component taken alone); INNER_ROUND = the components with WALL == 0.  They are reduced on the device from the table.
+ * The look checks itself: every label the sweep meets has a component number, and the areas of the table add up to the
+ * AREA of the components look; a violation is CHS_ECHECK.  Arguments and states are checked as by chs_components, with the
+ * same codes in the same order; `rows` must be the COUNT of the last shapes look.  The run does not notice the look. */
+#define CHS_SH_COLS 16
+#define CHS_SH_FIRST 0
+#define CHS_SH_AREA 1
+#define CHS_SH_PAIRS_H 2
+#define CHS_SH_PAIRS_V 3
+#define CHS_SH_PAIRS_D 4
+#define CHS_SH_TRIPLES 5
+#define CHS_SH_QUADS 6
+#define CHS_SH_WALL 7
+#define CHS_SH_SI 8
+#define CHS_SH_SJ 9
+#define CHS_SH_SII 10
+#define CHS_SH_SJJ 11
+#define CHS_SH_SIJ 12
+#define CHS_SH_SU_FIX 13
+#define CHS_SH_SUU_FIX 14
+#define CHS_SH_N_OUTSIDE 15
+#define CHS_SH_WORDS 17
+#define CHS_SH_SUM_AREA 7
+#define CHS_SH_SUM_PAIRS_H 8
+#define CHS_SH_SUM_PAIRS_V 9
+#define CHS_SH_SUM_PAIRS_D 10
+#define CHS_SH_SUM_TRIPLES 11
+#define CHS_SH_SUM_QUADS 12
+#define CHS_SH_SUM_WALL 13
+#define CHS_SH_SUM_N_OUTSIDE 14
+#define CHS_SH_HOLES 15
+#define CHS_SH_INNER_ROUND 16
+int chs_shapes(chs_handle h, double threshold, int32_t connectivity, int32_t side, int64_t out[CHS_SH_WORDS]);
+int chs_shapes_table(chs_handle h, int64_t rows, int64_t* out);   /* [rows][CHS_SH_COLS]; rows == COUNT of the last shapes look */
+/* Device time (ms, HIP events) of the sweep and the summary of the handle's last shapes look alone: the labelling before
+ * them is timed by chs_components_last_ms. */
+int chs_shapes_last_ms(chs_handle h, double* ms);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -761,6 +830,12 @@ int chs_batch_contour(chs_batch b, int32_t member, double threshold, int32_t bin
 int chs_batch_contour_hist(chs_batch b, int32_t bins, int64_t* out);
 int chs_batch_contour_map(chs_batch b, int64_t n, double* out);
 int chs_batch_contour_last_ms(chs_batch b, double* ms);
+/* chs_shapes of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of component buffers and one
+ * set of shape buffers for the batch, so the tables are those of the batch's last look, whichever member it was.  Words
+ * and table are those of the member's single handle on the same field.  The members' states, fields and records stay
+ * untouched. */
+int chs_batch_shapes(chs_batch b, int32_t member, double threshold, int32_t connectivity, int32_t side, int64_t out[CHS_SH_WORDS]);
+int chs_batch_shapes_table(chs_batch b, int64_t rows, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Scratch (spill) bytes, VGPRs and code size of every kernel of the two fast-engine translation units, compiled for
-gfx950 (no GPU needed).  `--row-zero`: exit 1 unless every k_row_* instantiation at N = 4096 and N = 8192 -- the step
-kernels of BASELINE.json's configs[2] and configs[3] and their once-per-call siblings -- has ScratchSize 0
-(tests/test_host.py runs this)."""
+"""Scratch (spill) bytes, VGPRs and code size of every kernel of the two fast-engine translation units and of the shapes
+look, compiled for gfx950 (no GPU needed).  `--row-zero`: exit 1 unless every k_row_* instantiation at N = 4096 and
+N = 8192 -- the step kernels of BASELINE.json's configs[2] and configs[3] and their once-per-call siblings -- and every
+k_sh_* kernel of chs_shapes.hip has ScratchSize 0 (tests/test_host.py runs this)."""
 import os
 import re
 import subprocess
@@ -27,7 +27,7 @@ def kernels(src):
         sc = re.search(r'; ScratchSize: (\d+)', body)
         vg = re.search(r'; NumVgprs: (\d+)', body)
         cl = re.search(r'; codeLenInByte = (\d+)', body)
-        if sc and '__global__' not in d and d.startswith('void k_'):
+        if sc and '__global__' not in d and (d.startswith('void k_') or d.startswith('k_')):
             short = re.sub(r'FCfg<([^>]*)>', lambda m: 'FCfg<' + m.group(1).replace(' ', '') + '>', d).split('(')[0]
             res.append((short, int(sc.group(1)), int(vg.group(1)) if vg else -1, int(cl.group(1)) if cl else -1))
     return res
@@ -35,9 +35,10 @@ def kernels(src):
 
 def main():
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(2) as pool:   # the two element types compile side by side
-        parts = list(pool.map(lambda tu: kernels(os.path.join(ROOT, 'chsimpy_amd', 'csrc', tu)), ('chs_fast_f64.hip', 'chs_fast_f32.hip')))
-    rows = parts[0] + parts[1]
+    with ThreadPoolExecutor(3) as pool:   # the two element types compile side by side
+        parts = list(pool.map(lambda tu: kernels(os.path.join(ROOT, 'chsimpy_amd', 'csrc', tu)),
+                              ('chs_fast_f64.hip', 'chs_fast_f32.hip', 'chs_shapes.hip')))
+    rows = parts[0] + parts[1] + parts[2]
     bad = []
     for name, sc, vg, cl in rows:
         big = re.search(r'FCfg<(double|float),(4096|8192),', name) is not None
@@ -45,8 +46,10 @@ def main():
             print(f"{sc:5d} B scratch  {vg:4d} vgpr  {cl:6d} B code  {name[-120:]}")
         if big and name.startswith('void k_row_') and sc != 0:
             bad.append((name, sc))
+        if 'k_sh_' in name and sc != 0:
+            bad.append((name, sc))
     if '--row-zero' in sys.argv and bad:
-        print('row kernels with scratch at N >= 4096:', bad)
+        print('row kernels at N >= 4096 or shapes kernels with scratch:', bad)
         sys.exit(1)
 
 
