@@ -40,6 +40,7 @@ CHS_CT_SUMS = 6               # its float64 sums: txx, txy, tyy, k1, ka, k2
 CHS_CT_MAX_BINS = 1024        # bins of its curvature histogram at most
 CHS_SH_WORDS = 17             # int64 words of chs_shapes (chsimpy_amd/shapes.py names them)
 CHS_SH_COLS = 16              # int64 columns of its table
+CHS_TR_WORDS = 25             # int64 words of chs_track (chsimpy_amd/tracking.py names them)
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -70,6 +71,8 @@ SYMBOLS = (
     'chs_contour', 'chs_contour_hist', 'chs_contour_map', 'chs_contour_last_ms', 'chs_contour_tile',
     'chs_batch_contour', 'chs_batch_contour_hist', 'chs_batch_contour_map', 'chs_batch_contour_last_ms',
     'chs_shapes', 'chs_shapes_table', 'chs_shapes_last_ms', 'chs_batch_shapes', 'chs_batch_shapes_table',
+    'chs_track', 'chs_track_pairs', 'chs_track_reset', 'chs_track_last_ms',
+    'chs_batch_track', 'chs_batch_track_pairs', 'chs_batch_track_reset',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -255,6 +258,13 @@ def load():
     lib.chs_shapes_last_ms.argtypes = [vp, dp]
     lib.chs_batch_shapes.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, i64p]
     lib.chs_batch_shapes_table.argtypes = [vp, C.c_int64, i64p]
+    lib.chs_track.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, i64p]
+    lib.chs_track_pairs.argtypes = [vp, C.c_int64, i64p]
+    lib.chs_track_reset.argtypes = [vp]
+    lib.chs_track_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_track.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, i64p]
+    lib.chs_batch_track_pairs.argtypes = [vp, C.c_int64, i64p]
+    lib.chs_batch_track_reset.argtypes = [vp, C.c_int32]
     # engines parked by chs_destroy are device memory of this process: hand them back at interpreter exit
     import atexit
     atexit.register(lib.chs_pool_clear)
@@ -628,6 +638,28 @@ class _Looks:
         words = self._shapes(lead, threshold, connectivity, side)
         return words, self.shapes_table(), self.components_table(), (self.components_labels() if labels else None)
 
+    _tr_pairs = 0
+
+    def _track(self, lead, threshold, connectivity, side, keep):
+        out = np.empty(CHS_TR_WORDS, dtype=np.int64)
+        self._look_call('track', *lead, float(threshold), int(connectivity), int(side), 1 if keep else 0, _i64ptr(out))
+        self._sh_count = self._cc_count = int(out[0])      # (a track look is a shapes and a components look too)
+        self._tr_pairs = int(out[19])                      # CHS_TR_PAIRS
+        return out
+
+    def track_pairs(self):
+        """int64 [pairs][3] of the last track look: the rows (a, b, n), sorted by (a, b)."""
+        out = np.empty((self._tr_pairs, 3), dtype=np.int64)
+        self._look_call('track_pairs', self._tr_pairs, _i64ptr(out))
+        return out
+
+    def _track_look(self, lead, threshold, connectivity, side, keep):
+        words = self._track(lead, threshold, connectivity, side, keep)
+        return words, self.track_pairs(), self.shapes_table(), self.components_table()
+
+    def _track_reset(self, lead):
+        self._look_call('track_reset', *lead)
+
     @staticmethod
     def two_point_max_r(N):
         return two_point_max_r(N)
@@ -830,6 +862,23 @@ class Engine(_Looks):
     def shapes_ms(self):
         """Device time (ms) of the sweep and the summary of the last `shapes`."""
         return self._last_ms('chs_shapes_last_ms')
+
+    def track(self, threshold, connectivity=4, side=CHS_CC_BELOW, keep=True):
+        """The 25 int64 words of a track look at the field the device holds (chs_track; chsimpy_amd/tracking.py names
+        them).  The pair table of this look: `track_pairs`; it is a shapes and a components look as well."""
+        return self._track((), threshold, connectivity, side, keep)
+
+    def track_look(self, threshold, connectivity, side, keep=True):
+        """(words, pairs, shape table, component table) of one track look."""
+        return self._track_look((), threshold, connectivity, side, keep)
+
+    def track_reset(self):
+        """Drop the frame (chs_track_reset): the next track look finds none."""
+        self._track_reset(())
+
+    def track_ms(self):
+        """Device time (ms) of the overlap passes of the last `track`."""
+        return self._last_ms('chs_track_last_ms')
 
     def morphology_ms(self):
         """Device time (ms) of the last `morphology`."""
@@ -1034,6 +1083,17 @@ class Batch(_Looks):
 
     def shapes_look(self, member, threshold, connectivity, side, labels=False):
         return self._shapes_look((int(member),), threshold, connectivity, side, labels)
+
+    def track(self, member, threshold, connectivity=4, side=CHS_CC_BELOW, keep=True):
+        """`Engine.track` of one member (chs_batch_track): the frame is the member's own."""
+        return self._track((int(member),), threshold, connectivity, side, keep)
+
+    def track_look(self, member, threshold, connectivity, side, keep=True):
+        return self._track_look((int(member),), threshold, connectivity, side, keep)
+
+    def track_reset(self, member):
+        """Drop the frame of one member (chs_batch_track_reset)."""
+        self._track_reset((int(member),))
 
     def get_state(self, member):
         s = chs_state()

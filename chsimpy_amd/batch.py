@@ -128,7 +128,7 @@ class _Member:
 
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
               'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look', 'shapes',
-              'shapes_look')
+              'shapes_look', 'track', 'track_look', 'track_reset')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -326,6 +326,11 @@ class BatchSolver:
     def shapes(self, member=None, threshold=None, connectivity=4, side='below', labels=False):
         """The members' droplet shapes (`Solver.shapes`), a `shapes.Shapes` each: _member_by_member."""
         return self._member_by_member('shapes', member, threshold, connectivity, side, labels)
+
+    def track(self, member=None, threshold=None, connectivity=4, side='below', keep=True, reset=False):
+        """The members' droplet tracking (`Solver.track`), a `tracking.Track` each: _member_by_member.  Every member keeps
+        its own frame on the device."""
+        return self._member_by_member('track', member, threshold, connectivity, side, keep, reset)
 
     def close(self, fetch_U=True):
         """Free the device batch; the members' fields are downloaded first unless the caller needs scalars only."""

@@ -169,6 +169,8 @@ struct Batch {
   void* tp = nullptr;            // chs_batch_two_point: the batch's one set of buffers (chs_two_point.hip), at the first look
   void* ct = nullptr;            // chs_batch_contour: the batch's one set of buffers (chs_contour.hip), at the first look
   void* sh = nullptr;            // chs_batch_shapes: the batch's one set of buffers (chs_shapes.hip), at the first look
+  void* tr = nullptr;            // chs_batch_track: the batch's one hash table and row list (chs_track.hip), at the first look;
+                                 // the frames are the members' own (Engine::tr)
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -193,6 +195,7 @@ void batch_free(Batch* b) {
   chs_tp_free(&b->tp);
   chs_ct_free(&b->ct);
   chs_sh_free(&b->sh);
+  chs_tr_free(&b->tr);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -956,4 +959,30 @@ extern "C" int chs_batch_shapes_table(chs_batch h, int64_t rows, int64_t* out) {
   Batch* b = as_batch(h);
   if (!b) return bad("chs_batch_shapes_table: null handle");
   return chs_sh_table(b->sh, b->m[0]->hc.device, b->stream, rows, out, "chs_batch_shapes_table");
+}
+
+// The droplet tracking of one member: the single handle's look on the batch's stream.  The frame is the member's own (in
+// its Engine, allocated at its first track look); the component and shape buffers, the hash table and the row list are
+// the batch's one set.
+extern "C" int chs_batch_track(chs_batch h, int32_t member, double threshold, int32_t connectivity, int32_t side, int32_t keep,
+                               int64_t out[CHS_TR_WORDS]) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_track: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_track: no such member");
+  Engine* E = b->m[(size_t)member];
+  return chs_tr_look(E, b->stream, &b->cc, &b->sh, &E->tr, &b->tr, threshold, connectivity, side, keep, out, "chs_batch_track");
+}
+
+extern "C" int chs_batch_track_pairs(chs_batch h, int64_t rows, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_track_pairs: null handle");
+  return chs_tr_pairs(b->tr, rows, out, "chs_batch_track_pairs");
+}
+
+extern "C" int chs_batch_track_reset(chs_batch h, int32_t member) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_track_reset: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_track_reset: no such member");
+  chs_tr_reset(b->m[(size_t)member]->tr);
+  return CHS_OK;
 }

@@ -316,6 +316,7 @@ struct Engine {
   double lastStepMs = 0.0;
   StepTimer timer;
   std::vector<double> hLambda;  // the eigenvalue table the engine was created with (engine pool: chs_create)
+  void* tr = nullptr;          // droplet tracking: the frame, hash table, rows, events (chs_track.hip), at the first track look
 };
 
 void chs_set_error(const std::string& s);
@@ -459,6 +460,19 @@ int chs_sh_table(void* buf, int device, hipStream_t s, int64_t rows, int64_t* ou
 int chs_sh_last_ms(const void* h, const void* buf, double* ms, const char* what);
 void chs_sh_free(void** buf);
 void chs_sh_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- droplet tracking (chs_track.hip) -------------------------------------------
+// The pair table of E's field thresholded at `threshold` against the frame an earlier track look kept (DESIGN.md section
+// 3l) on stream `s`: a shapes look with *ccbuf and *shbuf first (they stay that look's snapshot), then the overlap.
+// *frame holds the frame -- the handle's own, in a batch the member's -- and *work the hash table, the row list and the
+// last look's rows -- the same set for a single handle, the batch's one set otherwise; both are allocated here at the
+// first look: out[CHS_TR_WORDS].  The rows of the last look of a working set: chs_tr_pairs.
+int chs_tr_look(Engine* E, hipStream_t s, void** ccbuf, void** shbuf, void** frame, void** work, double threshold,
+                int32_t connectivity, int32_t side, int32_t keep, int64_t* out, const char* who);
+int chs_tr_pairs(void* work, int64_t rows, int64_t* out, const char* who);
+void chs_tr_reset(void* frame);   // the frame goes; the buffers, the last pair table and the last time stay
+void chs_tr_free(void** buf);
+void chs_tr_forget(void* buf);    // the buffers stay, the frame and the last look go
 
 // ---- distance transform (chs_distance.hip) -----------------------------------
 // The squared distances of E's field thresholded at `threshold` on stream `s` with the buffer set

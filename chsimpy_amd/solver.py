@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, composition, contour, distance, morphology, mport, shapes, spectrum, two_point
+from . import _lib, chords, components, composition, contour, distance, morphology, mport, shapes, spectrum, tracking, two_point
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -294,6 +294,41 @@ class Solver:
         co = components.Components(words[:components.CHS_CC_WORDS], self.params.N, t, conn, code, table=cctab, labels=lab,
                                    delx=self.solution.delx)
         return shapes.Shapes(words, tab, co)
+
+    def track(self, threshold=None, connectivity=4, side='below', keep=True, reset=False):
+        """The droplets of the field the device holds against those of the last track look that was kept: which droplet
+        of then is which droplet of now, what merged, split, vanished or was born, and how the continued ones grew -- a
+        self-contained `tracking.Track` from one shapes look and the overlap passes on the device between two calls,
+        which the run does not notice.  The device keeps the number image of the kept look (the frame) and overlaps it
+        with the labelling of now; only the pair table and the two tables of `shapes` leave the device.  ``keep=True``
+        makes this look the frame of the next one; ``keep=False`` leaves the frame, which compares many later times
+        against one reference; ``reset=True`` drops the frame first.  The first look (and one after a reset) finds no
+        frame: its `Track` has ``have_prev`` False and nothing to link.  Foreground, ``connectivity`` and ``side`` are
+        those of `components` and need not be the frame's.  Overlap tracking assumes looks close enough in time that a
+        droplet overlaps itself.  A field the host edited is pushed first, as solve_or_resume does.  Needs a field:
+        prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        conn, code = components.check_connectivity(connectivity), components.side_code(side)
+        eng = self._look_engine()
+        held = self.__dict__.get('_track_prev')
+        if held is not None and held[0] is not eng:          # (the frame went with the engine that held it)
+            held = self._track_prev = None
+        if reset:
+            eng.track_reset()
+            held = self._track_prev = None
+        words, pairs, tab, cctab = eng.track_look(t, conn, code, keep)
+        co = components.Components(words[:components.CHS_CC_WORDS], self.params.N, t, conn, code, table=cctab,
+                                   delx=self.solution.delx)
+        now = shapes.Shapes(words[:shapes.CHS_SH_WORDS], tab, co)
+        steps = self.solution.computed_steps
+        at = (None if steps is None else int(steps), float(self.time_passed))
+        if words[tracking.CHS_TR_HAVE_PREV] and held is None:
+            raise ValueError("the device holds a frame that this Solver did not take: track(reset=True) starts anew")
+        prev, was = (held[1], held[2]) if words[tracking.CHS_TR_HAVE_PREV] else (None, (None, None))
+        out = tracking.Track(words, pairs, prev, now, steps=(was[0], at[0]), times=(was[1], at[1]))
+        if keep:
+            self._track_prev = (eng, now, at)
+        return out
 
     # -- solver.py:84-135 ----------------------------------------------------------
     def prepare(self):

@@ -718,6 +718,50 @@ int chs_shapes_table(chs_handle h, int64_t rows, int64_t* out);   /* [rows][CHS_
  * them is timed by chs_components_last_ms. */
 int chs_shapes_last_ms(chs_handle h, double* ms);
 
+/* ---- Droplet tracking: the labelling of now overlapped with that of an earlier look ---------
+ * A FRAME is the component-number image of a track look: int32 [N][N], -1 for background, the numbering that of
+ * chs_components (by ascending `first`), together with its count CA and its (threshold, connectivity, side).  A handle
+ * keeps at most one frame, on the device.
+ * Pixel p has a = frame[p] and b = its number in the current look; its key is (a, b).  The PAIR TABLE is int64 [P][3]: one
+ * row (a, b, n) for every key other than (-1, -1) that at least one pixel has, n being the number of such pixels, the rows
+ * sorted by (a, b).  Rows with b = -1 are the pixels droplet a lost to the background, rows with a = -1 the ground
+ * droplet b gained from it.  Every cell is an integer and every accumulation an integer add, so the table does not depend
+ * on the order the device worked in: it is the numpy model's (chsimpy_amd/tracking.py) bit for bit, for both element types.
+ * A track look IS a shapes look (and so a components look) of the same (threshold, connectivity, side): arguments and
+ * states are checked by it, the same codes in the same order, and afterwards chs_shapes_table, chs_components_table and
+ * chs_components_labels return this labelling.  If the handle holds a frame, the look then overlaps the frame with the
+ * current labelling.  With keep != 0 the current number image becomes the frame (two images are swapped, nothing is
+ * copied); keep == 0 leaves the frame as it is, which compares many later times against one reference.  The frame's
+ * (threshold, connectivity, side) need not be the look's.
+ * The frame survives steps, chs_set_U and later chs_components and chs_shapes looks; it goes with chs_track_reset and with
+ * the handle.  A rejected call leaves the frame, the last pair table and the last time in place.
+ * Words, CHS_TR_WORDS int64: the 17 of chs_shapes; HAVE_PREV (1 where the look found a frame); PREV_COUNT = CA; PAIRS = P;
+ * OVERLAP, the pixels with a >= 0 and b >= 0; LOST, a >= 0 and b = -1; GAINED, a = -1 and b >= 0; HEADS, the pixels with a
+ * key other than (-1, -1) that differs from the key of the left and of the upper neighbour (a wall counts as different):
+ * the raster-first pixel of every key is one, so P <= HEADS, and HEADS sizes the hash table; SLOTS, the slots of that
+ * table, the power of two >= 2 HEADS and at least 1024.  Without a frame HAVE_PREV = 0 and the words behind it are 0.
+ * A table above 2 GiB (16 bytes a slot: more than 2^26 heads, which only noise at N > 8192 has) is refused with CHS_EHIP,
+ * the code of an allocation the device refuses, and a message.
+ * The look checks itself: the rows' n and the (-1, -1) pixels add up to N^2, the rows with a >= 0 to the frame's area, the
+ * rows with b >= 0 to the AREA of the components look, P <= HEADS, and no insert ran out of slots; a violation is
+ * CHS_ECHECK.  The run does not notice the look. */
+#define CHS_TR_WORDS 25
+#define CHS_TR_HAVE_PREV 17
+#define CHS_TR_PREV_COUNT 18
+#define CHS_TR_PAIRS 19
+#define CHS_TR_OVERLAP 20
+#define CHS_TR_LOST 21
+#define CHS_TR_GAINED 22
+#define CHS_TR_HEADS 23
+#define CHS_TR_SLOTS 24
+int chs_track(chs_handle h, double threshold, int32_t connectivity, int32_t side, int32_t keep, int64_t out[CHS_TR_WORDS]);
+int chs_track_pairs(chs_handle h, int64_t rows, int64_t* out);   /* [rows][3]; rows == PAIRS of the last track look */
+int chs_track_reset(chs_handle h);                               /* drop the frame; the buffers stay */
+/* Device time (ms, HIP events) of the overlap passes of the handle's last track look alone (the host's wait for HEADS
+ * between them left out): the labelling and the shape table before them are timed by chs_components_last_ms and
+ * chs_shapes_last_ms. */
+int chs_track_last_ms(chs_handle h, double* ms);
+
 const char* chs_last_error(void);
 const char* chs_version(void);
 
@@ -836,6 +880,15 @@ int chs_batch_contour_last_ms(chs_batch b, double* ms);
  * untouched. */
 int chs_batch_shapes(chs_batch b, int32_t member, double threshold, int32_t connectivity, int32_t side, int64_t out[CHS_SH_WORDS]);
 int chs_batch_shapes_table(chs_batch b, int64_t rows, int64_t* out);
+/* chs_track of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream.  The frame is per member, allocated
+ * at that member's first track look, and chs_batch_track_reset drops that member's; the component and shape buffers, the
+ * hash table and the row list are the batch's one set, so the tables and the pair table are those of the batch's last
+ * look, whichever member it was.  Words and pairs are those of the member's single handle on the same fields.  The
+ * members' states, fields and records stay untouched. */
+int chs_batch_track(chs_batch b, int32_t member, double threshold, int32_t connectivity, int32_t side, int32_t keep,
+                    int64_t out[CHS_TR_WORDS]);
+int chs_batch_track_pairs(chs_batch b, int64_t rows, int64_t* out);
+int chs_batch_track_reset(chs_batch b, int32_t member);
 
 #ifdef __cplusplus
 }

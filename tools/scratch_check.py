@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Scratch (spill) bytes, VGPRs and code size of every kernel of the two fast-engine translation units and of the shapes
-look, compiled for gfx950 (no GPU needed).  `--row-zero`: exit 1 unless every k_row_* instantiation at N = 4096 and
-N = 8192 -- the step kernels of BASELINE.json's configs[2] and configs[3] and their once-per-call siblings -- and every
-k_sh_* kernel of chs_shapes.hip has ScratchSize 0 (tests/test_host.py runs this)."""
+"""Scratch (spill) bytes, VGPRs and code size of every kernel of the two fast-engine translation units, of the shapes
+look and of the track look, compiled for gfx950 (no GPU needed).  `--row-zero`: exit 1 unless every k_row_* instantiation
+at N = 4096 and N = 8192 -- the step kernels of BASELINE.json's configs[2] and configs[3] and their once-per-call
+siblings -- every k_sh_* kernel of chs_shapes.hip and every k_tr_* kernel of chs_track.hip has ScratchSize 0
+(tests/test_host.py runs this)."""
 import os
 import re
 import subprocess
@@ -35,10 +36,10 @@ def kernels(src):
 
 def main():
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(3) as pool:   # the two element types compile side by side
+    with ThreadPoolExecutor(4) as pool:   # the two element types compile side by side
         parts = list(pool.map(lambda tu: kernels(os.path.join(ROOT, 'chsimpy_amd', 'csrc', tu)),
-                              ('chs_fast_f64.hip', 'chs_fast_f32.hip', 'chs_shapes.hip')))
-    rows = parts[0] + parts[1] + parts[2]
+                              ('chs_fast_f64.hip', 'chs_fast_f32.hip', 'chs_shapes.hip', 'chs_track.hip')))
+    rows = [r for part in parts for r in part]
     bad = []
     for name, sc, vg, cl in rows:
         big = re.search(r'FCfg<(double|float),(4096|8192),', name) is not None
@@ -46,10 +47,10 @@ def main():
             print(f"{sc:5d} B scratch  {vg:4d} vgpr  {cl:6d} B code  {name[-120:]}")
         if big and name.startswith('void k_row_') and sc != 0:
             bad.append((name, sc))
-        if 'k_sh_' in name and sc != 0:
+        if ('k_sh_' in name or 'k_tr_' in name) and sc != 0:
             bad.append((name, sc))
     if '--row-zero' in sys.argv and bad:
-        print('row kernels at N >= 4096 or shapes kernels with scratch:', bad)
+        print('row kernels at N >= 4096, shapes kernels or track kernels with scratch:', bad)
         sys.exit(1)
 
 
