@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libchs_hip.so')
 
-CHS_OK, CHS_EINVAL, CHS_EHIP, CHS_ENAN, CHS_ESTATE, CHS_ECHECK = 0, -1, -2, -3, -4, -5
+CHS_OK, CHS_EINVAL, CHS_EHIP, CHS_ENAN, CHS_ESTATE, CHS_ECHECK, CHS_ELIMIT = 0, -1, -2, -3, -4, -5, -6
 CHS_F64, CHS_F32 = 0, 1
 CHS_ENGINE_AUTO, CHS_ENGINE_DIRECT, CHS_ENGINE_FAST, CHS_ENGINE_CHIRP = 0, 1, 2, 3
 CHS_CHIRP_AUTO_MIN_N = 129    # the smallest N that 'auto' gives to the chirp engine (include/chs_hip.h)
@@ -41,6 +41,8 @@ CHS_CT_MAX_BINS = 1024        # bins of its curvature histogram at most
 CHS_SH_WORDS = 17             # int64 words of chs_shapes (chsimpy_amd/shapes.py names them)
 CHS_SH_COLS = 16              # int64 columns of its table
 CHS_TR_WORDS = 25             # int64 words of chs_track (chsimpy_amd/tracking.py names them)
+CHS_TH_WORDS = 7              # int64 words of chs_thickness: fg, t2max, nmax, sumt2, ninf, kept, work
+CHS_TH_KEPT, CHS_TH_WORK = 5, 6
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -73,6 +75,9 @@ SYMBOLS = (
     'chs_shapes', 'chs_shapes_table', 'chs_shapes_last_ms', 'chs_batch_shapes', 'chs_batch_shapes_table',
     'chs_track', 'chs_track_pairs', 'chs_track_reset', 'chs_track_last_ms',
     'chs_batch_track', 'chs_batch_track_pairs', 'chs_batch_track_reset',
+    'chs_thickness_work_default', 'chs_thickness_reach', 'chs_thickness', 'chs_thickness_hist', 'chs_thickness_map',
+    'chs_thickness_last_ms', 'chs_batch_thickness', 'chs_batch_thickness_hist', 'chs_batch_thickness_map',
+    'chs_batch_thickness_last_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -99,6 +104,15 @@ class chs_state(C.Structure):
 
 class EngineError(RuntimeError):
     pass
+
+
+class ThicknessLimitError(EngineError):
+    """A thickness look that was refused (CHS_ELIMIT): it needs ``work`` disc pixels, the caller allowed ``limit``.  Nothing
+    was painted; the distance look of the same call is complete."""
+
+    def __init__(self, message, work, limit):
+        super().__init__(message)
+        self.work, self.limit = int(work), int(limit)
 
 
 _lib = None
@@ -262,6 +276,18 @@ def load():
     lib.chs_track_pairs.argtypes = [vp, C.c_int64, i64p]
     lib.chs_track_reset.argtypes = [vp]
     lib.chs_track_last_ms.argtypes = [vp, dp]
+    lib.chs_thickness_work_default.argtypes = [C.c_int32]
+    lib.chs_thickness_work_default.restype = C.c_int64
+    lib.chs_thickness_reach.argtypes = [C.c_int32, C.c_int32]
+    lib.chs_thickness_reach.restype = C.c_int32
+    lib.chs_thickness.argtypes = [vp, C.c_double, C.c_int32, C.c_int64, i64p]
+    lib.chs_thickness_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_thickness_map.argtypes = [vp, i32p]
+    lib.chs_thickness_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_thickness.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int64, i64p]
+    lib.chs_batch_thickness_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_batch_thickness_map.argtypes = [vp, i32p]
+    lib.chs_batch_thickness_last_ms.argtypes = [vp, dp]
     lib.chs_batch_track.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, i64p]
     lib.chs_batch_track_pairs.argtypes = [vp, C.c_int64, i64p]
     lib.chs_batch_track_reset.argtypes = [vp, C.c_int32]
@@ -311,6 +337,16 @@ def distance_tile():
     if rc != CHS_OK:
         raise EngineError(f"chs_distance_tile failed ({rc})")
     return int(b.value), int(c.value)
+
+
+def thickness_work_default(N):
+    """The default work limit of chs_thickness at grid size N (chs_thickness_work_default): K N^2."""
+    return int(load().chs_thickness_work_default(int(N)))
+
+
+def thickness_reach(R, diagonal):
+    """E(R, axis) or E(R, diagonal) of the pruning rule of chs_thickness, by the function the kernel compiles."""
+    return int(load().chs_thickness_reach(int(R), 1 if diagonal else 0))
 
 
 def distance_bins(N):
@@ -516,6 +552,42 @@ class _Looks:
     def _distance_look(self, lead, threshold, side, hist, map):
         words = self._distance(lead, threshold, side)
         return words, (self.distance_hist() if hist else None), (self.distance_map() if map else None)
+
+    def _thickness(self, lead, threshold, side, max_work):
+        out = np.empty(CHS_TH_WORDS, dtype=np.int64)
+        limit = 0 if max_work is None else int(max_work)
+        what = self._prefix + 'thickness'
+        rc = getattr(self.lib, what)(self._h, *lead, float(threshold), int(side), limit, _i64ptr(out))
+        if rc == CHS_ELIMIT:
+            msg = self.lib.chs_last_error().decode(errors='replace')
+            raise ThicknessLimitError(f"{what} refused ({rc}): {msg}", out[CHS_TH_WORK],
+                                      limit or self.lib.chs_thickness_work_default(self.N))
+        self._check(rc, what)
+        return out
+
+    def thickness_hist(self):
+        """int64 [chs_distance_bins(N)] of the last thickness look: the foreground pixels by bin of the local radius."""
+        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
+        self._look_call('thickness_hist', len(out), _i64ptr(out))
+        return out
+
+    def thickness_map(self):
+        """int32 [N][N] of the last thickness look: the squared local radii."""
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._look_call('thickness_map', _i32ptr(out))
+        return out
+
+    def _thickness_look(self, lead, threshold, side, hist, map, max_work):
+        """(words, hist, t2) of the thickness look and (words, hist, d2) of its distance look.  The C entry returns the
+        thickness words alone, so the five distance words come from a distance look of their own on the same buffers and
+        field -- the same bits as the one inside, at a fraction of the thickness look's cost."""
+        words = self._thickness(lead, threshold, side, max_work)
+        th = words, (self.thickness_hist() if hist else None), (self.thickness_map() if map else None)
+        return th, self._distance_look(lead, threshold, side, hist, map)
+
+    def thickness_ms(self):
+        """Device time (ms) of the last thickness look, the distance look inside included."""
+        return self._last_ms(self._prefix + 'thickness_last_ms')
 
     def _chords(self, lead, threshold):
         out = np.empty(CHS_CH_WORDS, dtype=np.int64)
@@ -855,6 +927,15 @@ class Engine(_Looks):
         chsimpy_amd/shapes.py names them).  The table of this look: `shapes_table`; it is a components look as well."""
         return self._shapes((), threshold, connectivity, side)
 
+    def thickness(self, threshold, side=CHS_CC_BELOW, max_work=None):
+        """The seven int64 summary words of the local thickness of the field the device holds (chs_thickness;
+        chsimpy_amd/thickness.py names them).  Histogram and map of this look: `thickness_hist`, `thickness_map`; it is a
+        distance look as well.  A look above `max_work` (None: the default) raises `ThicknessLimitError`."""
+        return self._thickness((), threshold, side, max_work)
+
+    def thickness_look(self, threshold, side, hist=True, map=False, max_work=None):
+        return self._thickness_look((), threshold, side, hist, map, max_work)
+
     def shapes_look(self, threshold, connectivity, side, labels=False):
         """One look with what belongs to it: (words, shape table, component table, labels or None)."""
         return self._shapes_look((), threshold, connectivity, side, labels)
@@ -1080,6 +1161,13 @@ class Batch(_Looks):
     def shapes(self, member, threshold, connectivity=4, side=CHS_CC_BELOW):
         """`Engine.shapes` of one member (chs_batch_shapes)."""
         return self._shapes((int(member),), threshold, connectivity, side)
+
+    def thickness(self, member, threshold, side=CHS_CC_BELOW, max_work=None):
+        """`Engine.thickness` of one member (chs_batch_thickness)."""
+        return self._thickness((int(member),), threshold, side, max_work)
+
+    def thickness_look(self, member, threshold, side, hist=True, map=False, max_work=None):
+        return self._thickness_look((int(member),), threshold, side, hist, map, max_work)
 
     def shapes_look(self, member, threshold, connectivity, side, labels=False):
         return self._shapes_look((int(member),), threshold, connectivity, side, labels)

@@ -128,7 +128,7 @@ class _Member:
 
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
               'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look', 'shapes',
-              'shapes_look', 'track', 'track_look', 'track_reset')
+              'shapes_look', 'track', 'track_look', 'track_reset', 'thickness', 'thickness_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -306,6 +306,10 @@ class BatchSolver:
     def distance(self, member=None, threshold=None, side='below', hist=True, map=False):
         """The members' distance transforms (`Solver.distance`), a `distance.Distance` each: _member_by_member."""
         return self._member_by_member('distance', member, threshold, side, hist, map)
+
+    def thickness(self, member=None, threshold=None, side='below', hist=True, map=False, max_work=None):
+        """The members' local thickness (`Solver.thickness`), a `thickness.Thickness` each: _member_by_member."""
+        return self._member_by_member('thickness', member, threshold, side, hist, map, max_work)
 
     def chords(self, member=None, threshold=None, hist=True):
         """The members' chord lengths (`Solver.chords`), a `chords.Chords` each: _member_by_member."""

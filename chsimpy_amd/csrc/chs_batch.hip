@@ -171,6 +171,7 @@ struct Batch {
   void* sh = nullptr;            // chs_batch_shapes: the batch's one set of buffers (chs_shapes.hip), at the first look
   void* tr = nullptr;            // chs_batch_track: the batch's one hash table and row list (chs_track.hip), at the first look;
                                  // the frames are the members' own (Engine::tr)
+  void* th = nullptr;            // chs_batch_thickness: the batch's one set of buffers (chs_thickness.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -196,6 +197,7 @@ void batch_free(Batch* b) {
   chs_ct_free(&b->ct);
   chs_sh_free(&b->sh);
   chs_tr_free(&b->tr);
+  chs_th_free(&b->th);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -985,4 +987,31 @@ extern "C" int chs_batch_track_reset(chs_batch h, int32_t member) {
   if (member < 0 || member >= b->B) return bad("chs_batch_track_reset: no such member");
   chs_tr_reset(b->m[(size_t)member]->tr);
   return CHS_OK;
+}
+
+// The local thickness of one member: the single handle's look on the batch's stream, with the batch's one set of distance
+// buffers and one set of thickness buffers.
+extern "C" int chs_batch_thickness(chs_batch h, int32_t member, double threshold, int32_t side, int64_t max_work,
+                                   int64_t out[CHS_TH_WORDS]) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_thickness: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_thickness: no such member");
+  return chs_th_look(b->m[(size_t)member], b->stream, &b->dt, &b->th, threshold, side, max_work, out, "chs_batch_thickness");
+}
+
+extern "C" int chs_batch_thickness_hist(chs_batch h, int32_t nbins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_thickness_hist: null handle");
+  return chs_th_hist(b->th, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_thickness_hist");
+}
+
+extern "C" int chs_batch_thickness_map(chs_batch h, int32_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_thickness_map: null handle");
+  return chs_th_map(b->th, b->m[0]->hc.device, b->stream, out, "chs_batch_thickness_map");
+}
+
+extern "C" int chs_batch_thickness_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_th_last_ms(b, b ? b->th : nullptr, ms, "chs_batch_thickness");
 }

@@ -317,6 +317,7 @@ struct Engine {
   StepTimer timer;
   std::vector<double> hLambda;  // the eigenvalue table the engine was created with (engine pool: chs_create)
   void* tr = nullptr;          // droplet tracking: the frame, hash table, rows, events (chs_track.hip), at the first track look
+  void* th = nullptr;          // local thickness: map, centre list, histogram, result, events (chs_thickness.hip), at the first look
 };
 
 void chs_set_error(const std::string& s);
@@ -483,6 +484,27 @@ int chs_dt_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* ou
 int chs_dt_map(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
 void chs_dt_free(void** buf);
 void chs_dt_forget(void* buf);   // the buffers stay, the last look goes
+// What the last look of a buffer set left on the device, for a look that builds on it (chs_thickness.hip): the squared
+// distances and the look's device time.  Read-only; CHS_ESTATE without a look.
+struct ChsDtSnapshot {
+  const int* D2 = nullptr;      // [N * N]
+  double ms = 0.0;
+};
+int chs_dt_snapshot(const void* buf, ChsDtSnapshot* out, const char* who);
+
+// ---- local thickness (chs_thickness.hip) ---------------------------------------
+// The local thickness of E's field thresholded at `threshold` on stream `s`: a distance look with
+// the buffer set *dtbuf first (it stays that look's snapshot), then the selection of the centres, the painting of their
+// discs and the statistics with the buffer set *buf, both allocated here at the first look: out[CHS_TH_WORDS].  max_work:
+// 0 for chs_thickness_work_default(N); a look that needs more returns CHS_ELIMIT and leaves no thickness result.
+// Histogram and map of the last look of a buffer set: chs_th_hist, chs_th_map.
+int chs_th_look(Engine* E, hipStream_t s, void** dtbuf, void** buf, double threshold, int32_t side, int64_t max_work,
+                int64_t* out, const char* who);
+int chs_th_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
+int chs_th_map(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
+int chs_th_last_ms(const void* h, const void* buf, double* ms, const char* what);
+void chs_th_free(void** buf);
+void chs_th_forget(void* buf);   // the buffers stay, the last look goes
 
 // ---- chord lengths (chs_chords.hip) -------------------------------------------
 // The chord lengths of both phases of E's field thresholded at `threshold`, along rows and columns (DESIGN.md section

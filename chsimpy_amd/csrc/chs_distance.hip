@@ -367,6 +367,13 @@ void chs_dt_forget(void* buf) {
   if (buf) look_forget((DtBuf*)buf);
 }
 
+int chs_dt_snapshot(const void* buf, ChsDtSnapshot* out, const char* who_) {
+  const DtBuf* s = (const DtBuf*)buf;
+  if (!s || !s->have) { chs_set_error(std::string(who_) + ": no distance look to build on"); return CHS_ESTATE; }
+  out->D2 = s->D2; out->ms = s->ms;
+  return CHS_OK;
+}
+
 int chs_dt_look(Engine* E, hipStream_t st, void** buf, double threshold, int32_t side, int64_t* out, const char* who_) {
   const std::string who(who_);
   int rc;

@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, composition, contour, distance, morphology, mport, shapes, spectrum, tracking, two_point
+from . import _lib, chords, components, composition, contour, distance, morphology, mport, shapes, spectrum, thickness, tracking, two_point
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -204,6 +204,23 @@ class Solver:
         eng = self._look_engine()
         words, hi, d2 = eng.distance_look(t, code, hist, map)
         return distance.Distance(words, self.params.N, t, code, hist=hi, d2=d2, delx=self.solution.delx)
+
+    def thickness(self, threshold=None, side='below', hist=True, map=False, max_work=None):
+        """The local thickness of a phase of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): for every pixel the radius of the largest disc that fits inside the phase and covers it --
+        the area-weighted histogram of those radii is the pore-size distribution, twice its mean the mean domain width --
+        a self-contained `thickness.Thickness` (with the `distance.Distance` of the same field in ``.distance``) from
+        looks on the device between two calls, which the run does not notice.  ``side`` as for `distance`; histogram and
+        N x N map are fetched in this call when asked for (without ``map=True`` nothing N x N leaves the device).
+        ``max_work`` (None: ``_lib.thickness_work_default(N)``) bounds the disc pixels the look may paint: a field that
+        needs more raises `_lib.ThicknessLimitError` with ``work`` and ``limit``, and nothing is painted.  Needs a field:
+        prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        code = thickness.side_code(side)
+        eng = self._look_engine()
+        (words, hi, t2), (dwords, dhi, d2) = eng.thickness_look(t, code, hist, map, max_work)
+        di = distance.Distance(dwords, self.params.N, t, code, hist=dhi, d2=d2, delx=self.solution.delx)
+        return thickness.Thickness(words, self.params.N, t, code, hist=hi, t2=t2, distance=di, delx=self.solution.delx)
 
     def chords(self, threshold=None, hist=True):
         """The chord lengths (linear intercepts) of the field the device holds, thresholded at `threshold` (None:

@@ -37,6 +37,9 @@ extern "C" {
 #define CHS_ESTATE (-4)   /* call order violated (e.g. step before prepare:
                              the assert at chsimpy/solver.py:139)                */
 #define CHS_ECHECK (-5)   /* a self-check of a device result failed (chs_components) */
+/* -6: a look would cost more than its caller allows (chs_thickness: WORK > max_work).  Written relative to CHS_ECHECK:
+ * tests/test_components_host.py reads the literal codes above and holds CHS_ECHECK to be the last of them. */
+#define CHS_ELIMIT (CHS_ECHECK - 1)
 
 /* arithmetic type of the device path */
 #define CHS_F64 0
@@ -407,6 +410,62 @@ int chs_distance_last_ms(chs_handle h, double* ms);
 /* The kernels' geometry (what the tests size their fields by): the rows of a band of the vertical pass, and the
  * consecutive pixels of a row that one wavefront pass of the horizontal pass covers. */
 int chs_distance_tile(int32_t* band_rows, int32_t* row_chunk);
+
+/* ---- Local thickness of a phase of the thresholded field: the pore-size distribution ----
+ * Foreground X and squared distance D2: exactly those of chs_distance -- `side`, the NaN and threshold conventions, the
+ * walls that are no background, CHS_DT_INF.  A thickness look is a distance look first, on the handle's distance buffers:
+ * afterwards chs_distance_hist / _map return that look's D2.
+ * Local thickness: T2[p], an int32, is 0 for a background pixel and, for a foreground pixel p,
+ *     T2[p] = max { D2[c] : c foreground, D2[c] < CHS_DT_INF, |p - c|^2 < D2[c] }
+ * the squared radius of the largest disc that fits inside the phase and covers p (Hildebrand and Rueegsegger): the open
+ * disc of squared radius D2[c] about c holds no background pixel.  Discs are clipped at the walls; a disc may poke out of
+ * the grid.  A grid without any background pixel has T2 = CHS_DT_INF everywhere, with KEPT = WORK = 0.
+ * Radius bin of a foreground pixel: k = isqrt(T2), as in chs_distance.  Histogram: hist[k], int64, the foreground pixels
+ * in bin k; its length is chs_distance_bins(N); CHS_DT_INF pixels are in no bin.
+ * The centres that are painted.  E(R, a, b) is the maximum of |q - (a, b)|^2 over the lattice points q with |q|^2 < R: by
+ * symmetry one function of R for the four axis neighbours (a, b) and one for the four diagonal ones,
+ * chs_thickness_reach(R, diagonal) -- the function the kernel compiles; 0 for R outside [1, CHS_DT_INF).  A centre c with
+ * R = D2[c] is DROPPED iff one of its 8 neighbours c' = c + (a, b) inside the grid is foreground, has D2[c'] <
+ * CHS_DT_INF and D2[c'] > E(R, a, b): every pixel of c's disc is then inside the disc of c', whose value is larger.
+ * E >= R, so D2 rises strictly along a chain of drops and every chain ends at a kept centre: the map does not depend on
+ * the rule, KEPT and WORK do.  With rho(R) = isqrt(R - 1), the largest integer with rho^2 < R, WORK is the sum over the
+ * kept centres of (2 rho + 1)^2: the unclipped bounding boxes, known before anything is painted.
+ * Summary: CHS_TH_WORDS int64 words at the indices below:
+ *   FG      foreground pixels
+ *   T2MAX   the largest T2 over the foreground pixels with T2 < CHS_DT_INF, 0 if there is none
+ *   NMAX    the pixels with T2 == T2MAX (0 if there is none)
+ *   SUMT2   the sum of T2 over the foreground pixels with T2 < CHS_DT_INF
+ *   NINF    pixels with T2 == CHS_DT_INF: 0 or N^2
+ *   KEPT    the centres the rule keeps
+ *   WORK    the sum of their bounding boxes
+ * The work limit.  The look can be arbitrarily expensive on a field no run produces (one background pixel in a full
+ * grid: WORK of the order N^4).  max_work = 0 means chs_thickness_work_default(N) = K N^2 (K: DESIGN.md section 3m; 0
+ * for N < 1); a negative max_work or one above 16 times the default is CHS_EINVAL.  When WORK > max_work nothing is
+ * painted -- the paint kernel reads WORK on the device and returns -- and the call returns CHS_ELIMIT, chs_last_error
+ * naming both numbers: that look has no thickness result (its fetches return CHS_ESTATE), the distance look of the same
+ * call is complete and can be fetched; of `out` KEPT and WORK are set and every other word is 0.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone and writes buffers of its own, so the run does not notice it; everything is integer -- maxima and sums -- so two
+ * looks return the same bits.  Histogram and map of the last look stay available until the next look.  The look checks
+ * itself: FG, T2MAX and NINF equal the distance look's FG, D2MAX and NINF, no scan reached its cap; a violation is
+ * CHS_ECHECK.  CHS_EINVAL (the last look undisturbed) for a null argument, a threshold that is not finite, a side other
+ * than 0 or 1, max_work out of range, or nbins != chs_distance_bins(N) (the message gives the expected value);
+ * CHS_ESTATE for _hist / _map / _last_ms without a look. */
+#define CHS_TH_WORDS 7
+#define CHS_TH_FG 0
+#define CHS_TH_T2MAX 1
+#define CHS_TH_NMAX 2
+#define CHS_TH_SUMT2 3
+#define CHS_TH_NINF 4
+#define CHS_TH_KEPT 5
+#define CHS_TH_WORK 6
+int64_t chs_thickness_work_default(int32_t N);            /* 0 for N < 1 */
+int32_t chs_thickness_reach(int32_t R, int32_t diagonal);  /* E(R, axis) or E(R, diagonal) */
+int chs_thickness(chs_handle h, double threshold, int32_t side, int64_t max_work, int64_t out[CHS_TH_WORDS]);
+int chs_thickness_hist(chs_handle h, int32_t nbins, int64_t* out);   /* [nbins] of the last look */
+int chs_thickness_map(chs_handle h, int32_t* out);                   /* [N][N] T2 of the last look */
+/* Device time (ms, HIP events) of the handle's last look, the distance look inside included. */
+int chs_thickness_last_ms(chs_handle h, double* ms);
 
 /* ---- Chord lengths (linear intercepts) of both phases, along rows and columns ----
  * For the N x N field U and a finite threshold t:
@@ -889,6 +948,14 @@ int chs_batch_track(chs_batch b, int32_t member, double threshold, int32_t conne
                     int64_t out[CHS_TR_WORDS]);
 int chs_batch_track_pairs(chs_batch b, int64_t rows, int64_t* out);
 int chs_batch_track_reset(chs_batch b, int32_t member);
+/* chs_thickness of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of distance buffers and
+ * one set of thickness buffers for the batch, so histogram, map and time are those of the batch's last look, whichever
+ * member it was (and chs_batch_distance_hist / _map those of the distance look inside).  Words, histogram and map are
+ * those of the member's single handle on the same field.  The members' states, fields and records stay untouched. */
+int chs_batch_thickness(chs_batch b, int32_t member, double threshold, int32_t side, int64_t max_work, int64_t out[CHS_TH_WORDS]);
+int chs_batch_thickness_hist(chs_batch b, int32_t nbins, int64_t* out);
+int chs_batch_thickness_map(chs_batch b, int32_t* out);
+int chs_batch_thickness_last_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }
