@@ -43,6 +43,8 @@ CHS_SH_COLS = 16              # int64 columns of its table
 CHS_TR_WORDS = 25             # int64 words of chs_track (chsimpy_amd/tracking.py names them)
 CHS_TH_WORDS = 7              # int64 words of chs_thickness: fg, t2max, nmax, sumt2, ninf, kept, work
 CHS_TH_KEPT, CHS_TH_WORK = 5, 6
+CHS_GEO_WORDS = 16            # int64 words of chs_geodesic (chsimpy_amd/geodesic.py names them)
+CHS_GEO_ROUNDS, CHS_GEO_LIMIT = 14, 15
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -78,6 +80,9 @@ SYMBOLS = (
     'chs_thickness_work_default', 'chs_thickness_reach', 'chs_thickness', 'chs_thickness_hist', 'chs_thickness_map',
     'chs_thickness_last_ms', 'chs_batch_thickness', 'chs_batch_thickness_hist', 'chs_batch_thickness_map',
     'chs_batch_thickness_last_ms',
+    'chs_geodesic_bins', 'chs_geodesic_rounds_default', 'chs_geodesic', 'chs_geodesic_hist', 'chs_geodesic_profile',
+    'chs_geodesic_map', 'chs_geodesic_last_ms', 'chs_geodesic_relax_ms', 'chs_batch_geodesic', 'chs_batch_geodesic_hist',
+    'chs_batch_geodesic_profile', 'chs_batch_geodesic_map', 'chs_batch_geodesic_last_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -113,6 +118,15 @@ class ThicknessLimitError(EngineError):
     def __init__(self, message, work, limit):
         super().__init__(message)
         self.work, self.limit = int(work), int(limit)
+
+
+class GeodesicLimitError(EngineError):
+    """A geodesic look that ran out of rounds (CHS_ELIMIT): tiles were still active after ``rounds`` relaxation rounds, the
+    caller allowed ``limit``.  There is no geodesic result; the components look of the same call is complete."""
+
+    def __init__(self, message, rounds, limit):
+        super().__init__(message)
+        self.rounds, self.limit = int(rounds), int(limit)
 
 
 _lib = None
@@ -288,6 +302,21 @@ def load():
     lib.chs_batch_thickness_hist.argtypes = [vp, C.c_int32, i64p]
     lib.chs_batch_thickness_map.argtypes = [vp, i32p]
     lib.chs_batch_thickness_last_ms.argtypes = [vp, dp]
+    lib.chs_geodesic_bins.argtypes = [C.c_int32]
+    lib.chs_geodesic_bins.restype = C.c_int32
+    lib.chs_geodesic_rounds_default.argtypes = [C.c_int32]
+    lib.chs_geodesic_rounds_default.restype = C.c_int64
+    lib.chs_geodesic.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int64, i64p]
+    lib.chs_geodesic_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_geodesic_profile.argtypes = [vp, i64p]
+    lib.chs_geodesic_map.argtypes = [vp, i32p]
+    lib.chs_geodesic_last_ms.argtypes = [vp, dp]
+    lib.chs_geodesic_relax_ms.argtypes = [vp, dp]
+    lib.chs_batch_geodesic.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int64, i64p]
+    lib.chs_batch_geodesic_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_batch_geodesic_profile.argtypes = [vp, i64p]
+    lib.chs_batch_geodesic_map.argtypes = [vp, i32p]
+    lib.chs_batch_geodesic_last_ms.argtypes = [vp, dp]
     lib.chs_batch_track.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, i64p]
     lib.chs_batch_track_pairs.argtypes = [vp, C.c_int64, i64p]
     lib.chs_batch_track_reset.argtypes = [vp, C.c_int32]
@@ -347,6 +376,16 @@ def thickness_work_default(N):
 def thickness_reach(R, diagonal):
     """E(R, axis) or E(R, diagonal) of the pruning rule of chs_thickness, by the function the kernel compiles."""
     return int(load().chs_thickness_reach(int(R), 1 if diagonal else 0))
+
+
+def geodesic_bins(N):
+    """The length of the histogram of chs_geodesic at grid size N (chs_geodesic_bins): 4N."""
+    return int(load().chs_geodesic_bins(int(N)))
+
+
+def geodesic_rounds_default(N):
+    """The default round limit of chs_geodesic at grid size N (chs_geodesic_rounds_default): 32 nt^2 + 64."""
+    return int(load().chs_geodesic_rounds_default(int(N)))
 
 
 def distance_bins(N):
@@ -588,6 +627,51 @@ class _Looks:
     def thickness_ms(self):
         """Device time (ms) of the last thickness look, the distance look inside included."""
         return self._last_ms(self._prefix + 'thickness_last_ms')
+
+    def _geodesic(self, lead, threshold, connectivity, side, source, max_rounds):
+        out = np.empty(CHS_GEO_WORDS, dtype=np.int64)
+        limit = 0 if max_rounds is None else int(max_rounds)
+        what = self._prefix + 'geodesic'
+        rc = getattr(self.lib, what)(self._h, *lead, float(threshold), int(connectivity), int(side), int(source), limit,
+                                     _i64ptr(out))
+        if rc == CHS_ELIMIT:
+            msg = self.lib.chs_last_error().decode(errors='replace')
+            raise GeodesicLimitError(f"{what} refused ({rc}): {msg}", out[CHS_GEO_ROUNDS], out[CHS_GEO_LIMIT])
+        self._check(rc, what)
+        self._cc_count = int(out[12])                      # CHS_GEO_CC_COUNT (a geodesic look is a components look too)
+        return out
+
+    def geodesic_hist(self):
+        """int64 [chs_geodesic_bins(N)] of the last geodesic look: the reached pixels by G / UNIT."""
+        out = np.empty(int(self.lib.chs_geodesic_bins(self.N)), dtype=np.int64)
+        self._look_call('geodesic_hist', len(out), _i64ptr(out))
+        return out
+
+    def geodesic_profile(self):
+        """int64 [N][3] of the last geodesic look: foreground, reached and the sum of G by depth."""
+        out = np.empty((self.N, 3), dtype=np.int64)
+        self._look_call('geodesic_profile', _i64ptr(out))
+        return out
+
+    def geodesic_map(self):
+        """int32 [N][N] of the last geodesic look: G."""
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        self._look_call('geodesic_map', _i32ptr(out))
+        return out
+
+    def _geodesic_look(self, lead, threshold, connectivity, side, source, hist, profile, map, max_rounds):
+        """(words, hist or None, profile or None, G or None) of one geodesic look."""
+        words = self._geodesic(lead, threshold, connectivity, side, source, max_rounds)
+        return (words, self.geodesic_hist() if hist else None, self.geodesic_profile() if profile else None,
+                self.geodesic_map() if map else None)
+
+    def geodesic_ms(self):
+        """Device time (ms) of the last geodesic look, the components look inside included."""
+        return self._last_ms(self._prefix + 'geodesic_last_ms')
+
+    def geodesic_rounds_default(self):
+        """The default round limit of a geodesic look at this grid size."""
+        return int(self.lib.chs_geodesic_rounds_default(self.N))
 
     def _chords(self, lead, threshold):
         out = np.empty(CHS_CH_WORDS, dtype=np.int64)
@@ -936,6 +1020,20 @@ class Engine(_Looks):
     def thickness_look(self, threshold, side, hist=True, map=False, max_work=None):
         return self._thickness_look((), threshold, side, hist, map, max_work)
 
+    def geodesic(self, threshold, connectivity=8, side=CHS_CC_BELOW, source=0, max_rounds=None):
+        """The sixteen int64 words of the geodesic look at the field the device holds (chs_geodesic;
+        chsimpy_amd/geodesic.py names them).  Histogram, profile and map of this look: `geodesic_hist`,
+        `geodesic_profile`, `geodesic_map`; it is a components look as well.  A look that needs more than `max_rounds`
+        rounds (None: the default) raises `GeodesicLimitError`."""
+        return self._geodesic((), threshold, connectivity, side, source, max_rounds)
+
+    def geodesic_look(self, threshold, connectivity, side, source, hist=True, profile=True, map=False, max_rounds=None):
+        return self._geodesic_look((), threshold, connectivity, side, source, hist, profile, map, max_rounds)
+
+    def geodesic_relax_ms(self):
+        """Device time (ms) of the relaxation rounds of the last geodesic look."""
+        return self._last_ms('chs_geodesic_relax_ms')
+
     def shapes_look(self, threshold, connectivity, side, labels=False):
         """One look with what belongs to it: (words, shape table, component table, labels or None)."""
         return self._shapes_look((), threshold, connectivity, side, labels)
@@ -1168,6 +1266,13 @@ class Batch(_Looks):
 
     def thickness_look(self, member, threshold, side, hist=True, map=False, max_work=None):
         return self._thickness_look((int(member),), threshold, side, hist, map, max_work)
+
+    def geodesic(self, member, threshold, connectivity=8, side=CHS_CC_BELOW, source=0, max_rounds=None):
+        """`Engine.geodesic` of one member (chs_batch_geodesic)."""
+        return self._geodesic((int(member),), threshold, connectivity, side, source, max_rounds)
+
+    def geodesic_look(self, member, threshold, connectivity, side, source, hist=True, profile=True, map=False, max_rounds=None):
+        return self._geodesic_look((int(member),), threshold, connectivity, side, source, hist, profile, map, max_rounds)
 
     def shapes_look(self, member, threshold, connectivity, side, labels=False):
         return self._shapes_look((int(member),), threshold, connectivity, side, labels)

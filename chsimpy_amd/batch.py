@@ -128,7 +128,8 @@ class _Member:
 
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
               'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look', 'shapes',
-              'shapes_look', 'track', 'track_look', 'track_reset', 'thickness', 'thickness_look')
+              'shapes_look', 'track', 'track_look', 'track_reset', 'thickness', 'thickness_look',
+              'geodesic', 'geodesic_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -310,6 +311,11 @@ class BatchSolver:
     def thickness(self, member=None, threshold=None, side='below', hist=True, map=False, max_work=None):
         """The members' local thickness (`Solver.thickness`), a `thickness.Thickness` each: _member_by_member."""
         return self._member_by_member('thickness', member, threshold, side, hist, map, max_work)
+
+    def geodesic(self, member=None, threshold=None, connectivity=8, side='below', source='top', hist=True, profile=True, map=False,
+                 max_rounds=None):
+        """The members' geodesic looks (`Solver.geodesic`), a `geodesic.Geodesic` each: _member_by_member."""
+        return self._member_by_member('geodesic', member, threshold, connectivity, side, source, hist, profile, map, max_rounds)
 
     def chords(self, member=None, threshold=None, hist=True):
         """The members' chord lengths (`Solver.chords`), a `chords.Chords` each: _member_by_member."""

@@ -172,6 +172,7 @@ struct Batch {
   void* tr = nullptr;            // chs_batch_track: the batch's one hash table and row list (chs_track.hip), at the first look;
                                  // the frames are the members' own (Engine::tr)
   void* th = nullptr;            // chs_batch_thickness: the batch's one set of buffers (chs_thickness.hip), at the first look
+  void* geo = nullptr;           // chs_batch_geodesic: the batch's one set of buffers (chs_geodesic.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -198,6 +199,7 @@ void batch_free(Batch* b) {
   chs_sh_free(&b->sh);
   chs_tr_free(&b->tr);
   chs_th_free(&b->th);
+  chs_geo_free(&b->geo);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -1014,4 +1016,38 @@ extern "C" int chs_batch_thickness_map(chs_batch h, int32_t* out) {
 extern "C" int chs_batch_thickness_last_ms(chs_batch h, double* ms) {
   Batch* b = as_batch(h);
   return chs_th_last_ms(b, b ? b->th : nullptr, ms, "chs_batch_thickness");
+}
+
+// The geodesic look at one member: the single handle's look on the batch's stream, with the batch's one set of component
+// buffers and one set of geodesic buffers.
+extern "C" int chs_batch_geodesic(chs_batch h, int32_t member, double threshold, int32_t connectivity, int32_t side, int32_t source,
+                                  int64_t max_rounds, int64_t out[CHS_GEO_WORDS]) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_geodesic: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_geodesic: no such member");
+  return chs_geo_look(b->m[(size_t)member], b->stream, &b->cc, &b->geo, threshold, connectivity, side, source, max_rounds, out,
+                      "chs_batch_geodesic");
+}
+
+extern "C" int chs_batch_geodesic_hist(chs_batch h, int32_t nbins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_geodesic_hist: null handle");
+  return chs_geo_hist(b->geo, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_geodesic_hist");
+}
+
+extern "C" int chs_batch_geodesic_profile(chs_batch h, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_geodesic_profile: null handle");
+  return chs_geo_profile(b->geo, b->m[0]->hc.device, b->stream, out, "chs_batch_geodesic_profile");
+}
+
+extern "C" int chs_batch_geodesic_map(chs_batch h, int32_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_geodesic_map: null handle");
+  return chs_geo_map(b->geo, b->m[0]->hc.device, b->stream, out, "chs_batch_geodesic_map");
+}
+
+extern "C" int chs_batch_geodesic_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_geo_last_ms(b, b ? b->geo : nullptr, ms, "chs_batch_geodesic");
 }

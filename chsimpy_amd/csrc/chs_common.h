@@ -318,6 +318,7 @@ struct Engine {
   std::vector<double> hLambda;  // the eigenvalue table the engine was created with (engine pool: chs_create)
   void* tr = nullptr;          // droplet tracking: the frame, hash table, rows, events (chs_track.hip), at the first track look
   void* th = nullptr;          // local thickness: map, centre list, histogram, result, events (chs_thickness.hip), at the first look
+  void* geo = nullptr;         // geodesic look: map, tile flags, histogram, profile, result, events (chs_geodesic.hip), at the first look
 };
 
 void chs_set_error(const std::string& s);
@@ -448,8 +449,25 @@ struct ChsCcSnapshot {
   const int* id = nullptr;      // [N * N] at a root: its component number
   const int* table = nullptr;   // [count][CHS_CC_COLS]
   int64_t count = 0;
+  double ms = 0.0;              // the look's device time
 };
 int chs_cc_snapshot(const void* buf, ChsCcSnapshot* out, const char* who);
+
+// ---- geodesic look (chs_geodesic.hip) ------------------------------------------
+// The geodesic map of E's field thresholded at `threshold` from the wall `source` on stream `s`: a
+// components look with the buffer set *ccbuf first (it stays that look's snapshot), then the relaxation rounds and the
+// statistics with the buffer set *buf, both allocated here at the first look: out[CHS_GEO_WORDS].  max_rounds: 0 for
+// chs_geodesic_rounds_default(N); a look that needs more returns CHS_ELIMIT and leaves no geodesic result.  Histogram,
+// profile and map of the last look of a buffer set: chs_geo_hist, chs_geo_profile, chs_geo_map.
+int chs_geo_look(Engine* E, hipStream_t s, void** ccbuf, void** buf, double threshold, int32_t connectivity, int32_t side,
+                 int32_t source, int64_t max_rounds, int64_t* out, const char* who);
+int chs_geo_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
+int chs_geo_profile(void* buf, int device, hipStream_t s, int64_t* out, const char* who);
+int chs_geo_map(void* buf, int device, hipStream_t s, int32_t* out, const char* who);
+int chs_geo_last_ms(const void* h, const void* buf, double* ms, const char* what);
+int chs_geo_relax_ms(const void* h, const void* buf, double* ms, const char* what);   // the rounds alone
+void chs_geo_free(void** buf);
+void chs_geo_forget(void* buf);   // the buffers stay, the last look goes
 
 // ---- droplet shapes (chs_shapes.hip) -------------------------------------------
 // The shape table of E's field thresholded at `threshold` on stream `s`: a components look with

@@ -519,7 +519,7 @@ void chs_cc_forget(void* buf) {
 int chs_cc_snapshot(const void* buf, ChsCcSnapshot* out, const char* who_) {
   const CcBuf* s = (const CcBuf*)buf;
   if (!s || !s->have) { chs_set_error(std::string(who_) + ": no components look to build on"); return CHS_ESTATE; }
-  out->L = s->L; out->id = s->id; out->table = s->table; out->count = s->count;
+  out->L = s->L; out->id = s->id; out->table = s->table; out->count = s->count; out->ms = s->ms;
   return CHS_OK;
 }
 

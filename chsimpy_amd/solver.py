@@ -14,7 +14,7 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, composition, contour, distance, morphology, mport, shapes, spectrum, thickness, tracking, two_point
+from . import _lib, chords, components, composition, contour, distance, geodesic, morphology, mport, shapes, spectrum, thickness, tracking, two_point
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -221,6 +221,24 @@ class Solver:
         (words, hi, t2), (dwords, dhi, d2) = eng.thickness_look(t, code, hist, map, max_work)
         di = distance.Distance(dwords, self.params.N, t, code, hist=dhi, d2=d2, delx=self.solution.delx)
         return thickness.Thickness(words, self.params.N, t, code, hist=hi, t2=t2, distance=di, delx=self.solution.delx)
+
+    def geodesic(self, threshold=None, connectivity=8, side='below', source='top', hist=True, profile=True, map=False,
+                 max_rounds=None):
+        """The geodesic look at a phase of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): the length of the shortest path through the phase alone from the wall ``source`` ('top',
+        'bottom', 'left', 'right') to every pixel of the phase -- the geodesic tortuosity of the way across, the fraction
+        of the phase that can be reached from that face and how much of it within a given depth -- a self-contained
+        `geodesic.Geodesic` from a look on the device between two calls, which the run does not notice.  ``connectivity``
+        and ``side`` as for `components`; histogram, profile and N x N map are fetched in this call when asked for
+        (without ``map=True`` nothing N x N leaves the device).  ``max_rounds`` (None:
+        ``_lib.geodesic_rounds_default(N)``) bounds the relaxation rounds: a field that needs more raises
+        `_lib.GeodesicLimitError` with ``rounds`` and ``limit``.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        conn = components.check_connectivity(connectivity)
+        code, src = components.side_code(side), geodesic.source_code(source)
+        eng = self._look_engine()
+        words, hi, pr, g = eng.geodesic_look(t, conn, code, src, hist, profile, map, max_rounds)
+        return geodesic.Geodesic(words, self.params.N, t, conn, code, src, hist=hi, profile=pr, g=g, delx=self.solution.delx)
 
     def chords(self, threshold=None, hist=True):
         """The chord lengths (linear intercepts) of the field the device holds, thresholded at `threshold` (None:

@@ -37,7 +37,7 @@ extern "C" {
 #define CHS_ESTATE (-4)   /* call order violated (e.g. step before prepare:
                              the assert at chsimpy/solver.py:139)                */
 #define CHS_ECHECK (-5)   /* a self-check of a device result failed (chs_components) */
-/* -6: a look would cost more than its caller allows (chs_thickness: WORK > max_work).  Written relative to CHS_ECHECK:
+/* -6: a look would cost more than its caller allows (chs_thickness: WORK > max_work; chs_geodesic: max_rounds).  Written relative to CHS_ECHECK:
  * tests/test_components_host.py reads the literal codes above and holds CHS_ECHECK to be the last of them. */
 #define CHS_ELIMIT (CHS_ECHECK - 1)
 
@@ -466,6 +466,92 @@ int chs_thickness_hist(chs_handle h, int32_t nbins, int64_t* out);   /* [nbins] 
 int chs_thickness_map(chs_handle h, int32_t* out);                   /* [N][N] T2 of the last look */
 /* Device time (ms, HIP events) of the handle's last look, the distance look inside included. */
 int chs_thickness_last_ms(chs_handle h, double* ms);
+
+/* ---- Geodesic look at a phase of the thresholded field: tortuosity and reach ----
+ * Foreground, `side` (0 below, 1 above) and `connectivity` (4 or 8) are those of chs_components, with no wrap-around.  A
+ * geodesic look is a components look first, on the handle's component buffers: afterwards chs_components_table / _labels
+ * return that look.
+ * Source and target.  `source` is one of four walls: 0 is row 0, 1 is row N-1, 2 is column 0, 3 is column N-1.  The
+ * target is the opposite wall.  The depth k of a pixel is its distance in pixels from the source wall along that axis, 0
+ * to N-1.
+ * Steps.  A path moves from a foreground pixel to a foreground neighbour.  At connectivity 4 an axial step costs 1 and
+ * there is no diagonal step: UNIT = 1.  At connectivity 8 an axial step costs 3 and a diagonal step 4 (the 3-4 chamfer
+ * metric): UNIT = 3.  A diagonal step needs only its two end pixels to be foreground -- the rule that makes them one
+ * component at connectivity 8.  In free space G / UNIT lies within [0.9428, 1.0541] of the Euclidean length.
+ * The map.  G[p] is an int32: -1 for background, 0 for a foreground pixel on the source wall, otherwise the smallest
+ * cost of a path from any such pixel to p; CHS_GEO_INF (INT32_MAX) marks a foreground pixel that no path reaches.  At N =
+ * 8192 a path costs less than 4 * 2^26, so int32 holds.
+ * Result words: CHS_GEO_WORDS int64 words at the indices below:
+ *   FG               foreground pixels
+ *   SOURCES          foreground pixels on the source wall
+ *   REACHED          reached pixels, sources included
+ *   TARGET_FG        foreground pixels on the target wall
+ *   TARGET_REACHED   reached pixels on the target wall
+ *   GMIN_TARGET      smallest G on the target wall; -1 when none is reached
+ *   GMIN_TARGET_POS  smallest position along the wall (column for sources 0 and 1, row for 2 and 3) that has
+ *                    GMIN_TARGET; -1 when none
+ *   GSUM_TARGET      sum of G over the reached target pixels
+ *   GMAX             largest G of a reached pixel; -1 when none
+ *   GMAX_FIRST       smallest linear index i*N + j with G == GMAX; -1 when none
+ *   GSUM             sum of G over the reached pixels
+ *   UNIT             1 or 3
+ *   CC_COUNT         components of the components look
+ *   CC_REACHED       components that hold a source pixel
+ *   ROUNDS           relaxation rounds used (0 without a source pixel)
+ *   LIMIT            the round limit that applied
+ * Every word but ROUNDS is unique for a given field and arguments; ROUNDS may differ from look to look and is only ever
+ * compared with bounds.
+ * Histogram: chs_geodesic_bins(N) = 4N bins of int64.  Bin d counts the reached pixels with G / UNIT == d (integer
+ * division); the last bin takes everything at or beyond 4N - 1.  Its running sum is the accessible amount of phase within
+ * depth d of the face.
+ * Profile: [N][3] int64: for every depth k the foreground pixels, the reached pixels and the sum of G over the reached
+ * pixels of that line.  Line N-1 repeats TARGET_FG, TARGET_REACHED and GSUM_TARGET.
+ * The round limit.  The map is relaxed tile by tile (64 x 64) in rounds, a launch each, until no tile is active.
+ * max_rounds = 0 means chs_geodesic_rounds_default(N) = 32 nt^2 + 64, nt = ceil(N / 64): the rounds of a one-pixel
+ * serpentine corridor through the whole grid, plus slack.  A negative max_rounds or one above 16 times the default is
+ * CHS_EINVAL.  When the limit is used up and tiles are still active the call returns CHS_ELIMIT, chs_last_error naming
+ * the rounds and the limit: there is no geodesic result (its fetches return CHS_ESTATE), the components look of the call
+ * stays valid; of `out` ROUNDS and LIMIT are set and every other word is 0.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the labels
+ * of its components look and writes buffers of its own, so the run does not notice it.  The look checks itself in the
+ * sweep that fills the words: (a) for every reached pixel p and every foreground neighbour q under the step rule, G[q] <=
+ * G[p] + w; (b) every reached pixel with G > 0 has a neighbour q with G[q] + w == G[p]; (c) G == 0 holds exactly on the
+ * foreground of the source wall; (d) no unreached foreground pixel has a reached foreground neighbour -- (a) to (c)
+ * together prove that G holds the shortest-path costs.  Then REACHED equals the summed area of the components whose table
+ * row holds a source pixel, TARGET_REACHED > 0 exactly when one of them touches the target wall, and REACHED <= FG.  A
+ * violation is CHS_ECHECK.  The argument checks, in this order and before the last look is touched: a null argument, a
+ * threshold that is not finite, the connectivity, the side, the source, max_rounds (all CHS_EINVAL), then the field
+ * (CHS_ESTATE).  CHS_EINVAL for nbins != chs_geodesic_bins(N) (the message gives the expected value); CHS_ESTATE for
+ * _hist / _profile / _map / _last_ms without a look. */
+#define CHS_GEO_INF 0x7fffffff
+#define CHS_GEO_WORDS 16
+#define CHS_GEO_FG 0
+#define CHS_GEO_SOURCES 1
+#define CHS_GEO_REACHED 2
+#define CHS_GEO_TARGET_FG 3
+#define CHS_GEO_TARGET_REACHED 4
+#define CHS_GEO_GMIN_TARGET 5
+#define CHS_GEO_GMIN_TARGET_POS 6
+#define CHS_GEO_GSUM_TARGET 7
+#define CHS_GEO_GMAX 8
+#define CHS_GEO_GMAX_FIRST 9
+#define CHS_GEO_GSUM 10
+#define CHS_GEO_UNIT 11
+#define CHS_GEO_CC_COUNT 12
+#define CHS_GEO_CC_REACHED 13
+#define CHS_GEO_ROUNDS 14
+#define CHS_GEO_LIMIT 15
+int32_t chs_geodesic_bins(int32_t N);              /* 4N; 0 for N < 1 */
+int64_t chs_geodesic_rounds_default(int32_t N);    /* 32 nt^2 + 64; 0 for N < 1 */
+int chs_geodesic(chs_handle h, double threshold, int32_t connectivity, int32_t side, int32_t source, int64_t max_rounds,
+                 int64_t out[CHS_GEO_WORDS]);
+int chs_geodesic_hist(chs_handle h, int32_t nbins, int64_t* out);   /* [nbins] of the last look */
+int chs_geodesic_profile(chs_handle h, int64_t* out);               /* [N][3] of the last look */
+int chs_geodesic_map(chs_handle h, int32_t* out);                   /* [N][N] G of the last look */
+/* Device time (ms, HIP events) of the handle's last look, the components look inside included; _relax_ms: of its
+ * relaxation rounds alone, the host's looks at the round counter between them included. */
+int chs_geodesic_last_ms(chs_handle h, double* ms);
+int chs_geodesic_relax_ms(chs_handle h, double* ms);
 
 /* ---- Chord lengths (linear intercepts) of both phases, along rows and columns ----
  * For the N x N field U and a finite threshold t:
@@ -956,6 +1042,17 @@ int chs_batch_thickness(chs_batch b, int32_t member, double threshold, int32_t s
 int chs_batch_thickness_hist(chs_batch b, int32_t nbins, int64_t* out);
 int chs_batch_thickness_map(chs_batch b, int32_t* out);
 int chs_batch_thickness_last_ms(chs_batch b, double* ms);
+/* chs_geodesic of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of component buffers and
+ * one set of geodesic buffers for the batch, so histogram, profile, map and time are those of the batch's last look,
+ * whichever member it was (and chs_batch_components_table / _labels those of the components look inside).  Words,
+ * histogram, profile and map are those of the member's single handle on the same field.  The members' states, fields and
+ * records stay untouched. */
+int chs_batch_geodesic(chs_batch b, int32_t member, double threshold, int32_t connectivity, int32_t side, int32_t source,
+                       int64_t max_rounds, int64_t out[CHS_GEO_WORDS]);
+int chs_batch_geodesic_hist(chs_batch b, int32_t nbins, int64_t* out);
+int chs_batch_geodesic_profile(chs_batch b, int64_t* out);
+int chs_batch_geodesic_map(chs_batch b, int32_t* out);
+int chs_batch_geodesic_last_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }
