@@ -196,7 +196,8 @@ static int rearm(Engine* E, const chs_consts* c) {
   E->jitter = 0.0; E->jitterPcg = false;
   if (E->dNoise) { hipFree(E->dNoise); E->dNoise = nullptr; }
   E->nColMinCur = 0; E->lastStepMs = 0.0; E->timer.on = false;
-  chs_morph_forget(E->morph);   // (a handle from the pool has had no look: chs_morphology_last_ms)
+  chs_spectrum_forget(E->spec); // (a handle from the pool has had no look: chs_structure_factor_last_ms)
+  chs_morph_forget(E->morph);   // (... chs_morphology_last_ms)
   chs_cc_forget(E->cc);
   chs_dt_forget(E->dt);
   chs_ch_forget(E->ch);

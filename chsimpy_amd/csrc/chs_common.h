@@ -422,6 +422,7 @@ int chs_spectrum_one(Engine* E, double* ssum, int32_t nbins, const char* who);
 // *buf is the batch's own buffer set, allocated here at the first call and freed by chs_spectrum_free
 int chs_spectrum_all(Engine* const* m, int B, hipStream_t s, bool chirp, void** buf, double* ssum, int32_t nbins, const char* who);
 void chs_spectrum_free(void** buf);
+void chs_spectrum_forget(void* buf);   // the buffers stay, the times of the last call go
 
 // ---- morphology (chs_morphology.hip) ------------------------------------------
 // Bit-quad counts of the thresholded field: out[CHS_MORPH_WORDS] of one handle at *threshold ...

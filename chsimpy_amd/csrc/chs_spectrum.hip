@@ -375,6 +375,12 @@ void chs_spectrum_free(void** buf) {
   *buf = nullptr;
 }
 
+void chs_spectrum_forget(void* buf) {
+  if (!buf) return;
+  SpecBuf* s = (SpecBuf*)buf;
+  s->ms[0] = s->ms[1] = s->ms[2] = -1.0;
+}
+
 int chs_spectrum_one(Engine* E, double* ssum, int32_t nbins, const char* who) {
   int rc;
   if ((rc = check_args(E, ssum, nbins, who))) return rc;
