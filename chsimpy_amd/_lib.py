@@ -45,6 +45,8 @@ CHS_TH_WORDS = 7              # int64 words of chs_thickness: fg, t2max, nmax, s
 CHS_TH_KEPT, CHS_TH_WORK = 5, 6
 CHS_GEO_WORDS = 16            # int64 words of chs_geodesic (chsimpy_amd/geodesic.py names them)
 CHS_GEO_ROUNDS, CHS_GEO_LIMIT = 14, 15
+CHS_SK_WORDS = 17             # int64 words of chs_skeleton (chsimpy_amd/skeleton.py names them)
+CHS_SK_SUBITERS, CHS_SK_LIMIT = 15, 16
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -83,6 +85,9 @@ SYMBOLS = (
     'chs_geodesic_bins', 'chs_geodesic_rounds_default', 'chs_geodesic', 'chs_geodesic_hist', 'chs_geodesic_profile',
     'chs_geodesic_map', 'chs_geodesic_last_ms', 'chs_geodesic_relax_ms', 'chs_batch_geodesic', 'chs_batch_geodesic_hist',
     'chs_batch_geodesic_profile', 'chs_batch_geodesic_map', 'chs_batch_geodesic_last_ms',
+    'chs_skeleton_subiters_default', 'chs_skeleton', 'chs_skeleton_hist', 'chs_skeleton_plane', 'chs_skeleton_last_ms',
+    'chs_skeleton_thin_ms', 'chs_batch_skeleton', 'chs_batch_skeleton_hist', 'chs_batch_skeleton_plane',
+    'chs_batch_skeleton_last_ms', 'chs_batch_skeleton_thin_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -118,6 +123,16 @@ class ThicknessLimitError(EngineError):
     def __init__(self, message, work, limit):
         super().__init__(message)
         self.work, self.limit = int(work), int(limit)
+
+
+class SkeletonLimitError(EngineError):
+    """A skeleton look that ran out of sub-iterations (CHS_ELIMIT): a pixel was still deleted in sub-iteration ``subiters``,
+    within the last four of the ``limit`` the caller allowed.  There is no skeleton result; the distance look of the same
+    call is complete."""
+
+    def __init__(self, message, subiters, limit):
+        super().__init__(message)
+        self.subiters, self.limit = int(subiters), int(limit)
 
 
 class GeodesicLimitError(EngineError):
@@ -317,6 +332,18 @@ def load():
     lib.chs_batch_geodesic_profile.argtypes = [vp, i64p]
     lib.chs_batch_geodesic_map.argtypes = [vp, i32p]
     lib.chs_batch_geodesic_last_ms.argtypes = [vp, dp]
+    lib.chs_skeleton_subiters_default.argtypes = [C.c_int32]
+    lib.chs_skeleton_subiters_default.restype = C.c_int64
+    lib.chs_skeleton.argtypes = [vp, C.c_double, C.c_int32, C.c_int64, i64p]
+    lib.chs_skeleton_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_skeleton_plane.argtypes = [vp, u64p]
+    lib.chs_skeleton_last_ms.argtypes = [vp, dp]
+    lib.chs_skeleton_thin_ms.argtypes = [vp, dp]
+    lib.chs_batch_skeleton.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int64, i64p]
+    lib.chs_batch_skeleton_hist.argtypes = [vp, C.c_int32, i64p]
+    lib.chs_batch_skeleton_plane.argtypes = [vp, u64p]
+    lib.chs_batch_skeleton_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_skeleton_thin_ms.argtypes = [vp, dp]
     lib.chs_batch_track.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, i64p]
     lib.chs_batch_track_pairs.argtypes = [vp, C.c_int64, i64p]
     lib.chs_batch_track_reset.argtypes = [vp, C.c_int32]
@@ -381,6 +408,11 @@ def thickness_reach(R, diagonal):
 def geodesic_bins(N):
     """The length of the histogram of chs_geodesic at grid size N (chs_geodesic_bins): 4N."""
     return int(load().chs_geodesic_bins(int(N)))
+
+
+def skeleton_subiters_default(N):
+    """The default limit of the sub-iterations of chs_skeleton at grid size N (chs_skeleton_subiters_default): 4 N + 64."""
+    return int(load().chs_skeleton_subiters_default(int(N)))
 
 
 def geodesic_rounds_default(N):
@@ -672,6 +704,42 @@ class _Looks:
     def geodesic_rounds_default(self):
         """The default round limit of a geodesic look at this grid size."""
         return int(self.lib.chs_geodesic_rounds_default(self.N))
+
+    def _skeleton(self, lead, threshold, side, max_subiters):
+        out = np.empty(CHS_SK_WORDS, dtype=np.int64)
+        limit = 0 if max_subiters is None else int(max_subiters)
+        what = self._prefix + 'skeleton'
+        rc = getattr(self.lib, what)(self._h, *lead, float(threshold), int(side), limit, _i64ptr(out))
+        if rc == CHS_ELIMIT:
+            msg = self.lib.chs_last_error().decode(errors='replace')
+            raise SkeletonLimitError(f"{what} refused ({rc}): {msg}", out[CHS_SK_SUBITERS], out[CHS_SK_LIMIT])
+        self._check(rc, what)
+        return out
+
+    def skeleton_hist(self):
+        """int64 [chs_distance_bins(N)] of the last skeleton look: the skeleton pixels by bin of their half-width."""
+        out = np.empty(int(self.lib.chs_distance_bins(self.N)), dtype=np.int64)
+        self._look_call('skeleton_hist', len(out), _i64ptr(out))
+        return out
+
+    def skeleton_plane(self):
+        """uint64 [N][ceil(N / 64)] of the last skeleton look: the packed skeleton, bit j of word w column 64 w + j."""
+        out = np.empty((self.N, (self.N + 63) // 64), dtype=np.uint64)
+        self._look_call('skeleton_plane', out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return out
+
+    def _skeleton_look(self, lead, threshold, side, hist, map, max_subiters):
+        """(words, hist or None, packed plane or None) of one skeleton look."""
+        words = self._skeleton(lead, threshold, side, max_subiters)
+        return words, (self.skeleton_hist() if hist else None), (self.skeleton_plane() if map else None)
+
+    def skeleton_ms(self):
+        """Device time (ms) of the last skeleton look, the distance look inside included."""
+        return self._last_ms(self._prefix + 'skeleton_last_ms')
+
+    def skeleton_thin_ms(self):
+        """Device time (ms) of the sub-iterations of the last skeleton look."""
+        return self._last_ms(self._prefix + 'skeleton_thin_ms')
 
     def _chords(self, lead, threshold):
         out = np.empty(CHS_CH_WORDS, dtype=np.int64)
@@ -1034,6 +1102,16 @@ class Engine(_Looks):
         """Device time (ms) of the relaxation rounds of the last geodesic look."""
         return self._last_ms('chs_geodesic_relax_ms')
 
+    def skeleton(self, threshold, side=CHS_CC_BELOW, max_subiters=None):
+        """The seventeen int64 words of the skeleton look at the field the device holds (chs_skeleton;
+        chsimpy_amd/skeleton.py names them).  Histogram and packed plane of this look: `skeleton_hist`, `skeleton_plane`; it
+        is a distance look as well.  A look that needs more than `max_subiters` sub-iterations (None: the default) raises
+        `SkeletonLimitError`."""
+        return self._skeleton((), threshold, side, max_subiters)
+
+    def skeleton_look(self, threshold, side, hist=True, map=False, max_subiters=None):
+        return self._skeleton_look((), threshold, side, hist, map, max_subiters)
+
     def shapes_look(self, threshold, connectivity, side, labels=False):
         """One look with what belongs to it: (words, shape table, component table, labels or None)."""
         return self._shapes_look((), threshold, connectivity, side, labels)
@@ -1273,6 +1351,13 @@ class Batch(_Looks):
 
     def geodesic_look(self, member, threshold, connectivity, side, source, hist=True, profile=True, map=False, max_rounds=None):
         return self._geodesic_look((int(member),), threshold, connectivity, side, source, hist, profile, map, max_rounds)
+
+    def skeleton(self, member, threshold, side=CHS_CC_BELOW, max_subiters=None):
+        """`Engine.skeleton` of one member (chs_batch_skeleton)."""
+        return self._skeleton((int(member),), threshold, side, max_subiters)
+
+    def skeleton_look(self, member, threshold, side, hist=True, map=False, max_subiters=None):
+        return self._skeleton_look((int(member),), threshold, side, hist, map, max_subiters)
 
     def shapes_look(self, member, threshold, connectivity, side, labels=False):
         return self._shapes_look((int(member),), threshold, connectivity, side, labels)

@@ -129,7 +129,7 @@ class _Member:
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
               'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look', 'shapes',
               'shapes_look', 'track', 'track_look', 'track_reset', 'thickness', 'thickness_look',
-              'geodesic', 'geodesic_look')
+              'geodesic', 'geodesic_look', 'skeleton', 'skeleton_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -316,6 +316,10 @@ class BatchSolver:
                  max_rounds=None):
         """The members' geodesic looks (`Solver.geodesic`), a `geodesic.Geodesic` each: _member_by_member."""
         return self._member_by_member('geodesic', member, threshold, connectivity, side, source, hist, profile, map, max_rounds)
+
+    def skeleton(self, member=None, threshold=None, side='below', hist=True, map=False, max_subiters=None):
+        """The members' skeleton looks (`Solver.skeleton`), a `skeleton.Skeleton` each: _member_by_member."""
+        return self._member_by_member('skeleton', member, threshold, side, hist, map, max_subiters)
 
     def chords(self, member=None, threshold=None, hist=True):
         """The members' chord lengths (`Solver.chords`), a `chords.Chords` each: _member_by_member."""

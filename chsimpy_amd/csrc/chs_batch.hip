@@ -173,6 +173,7 @@ struct Batch {
                                  // the frames are the members' own (Engine::tr)
   void* th = nullptr;            // chs_batch_thickness: the batch's one set of buffers (chs_thickness.hip), at the first look
   void* geo = nullptr;           // chs_batch_geodesic: the batch's one set of buffers (chs_geodesic.hip), at the first look
+  void* sk = nullptr;            // chs_batch_skeleton: the batch's one set of buffers (chs_skeleton.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -200,6 +201,7 @@ void batch_free(Batch* b) {
   chs_tr_free(&b->tr);
   chs_th_free(&b->th);
   chs_geo_free(&b->geo);
+  chs_sk_free(&b->sk);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -1050,4 +1052,36 @@ extern "C" int chs_batch_geodesic_map(chs_batch h, int32_t* out) {
 extern "C" int chs_batch_geodesic_last_ms(chs_batch h, double* ms) {
   Batch* b = as_batch(h);
   return chs_geo_last_ms(b, b ? b->geo : nullptr, ms, "chs_batch_geodesic");
+}
+
+// The skeleton look at one member: the single handle's look on the batch's stream, with the batch's one set of distance
+// buffers and one set of skeleton buffers.
+extern "C" int chs_batch_skeleton(chs_batch h, int32_t member, double threshold, int32_t side, int64_t max_subiters,
+                                  int64_t out[CHS_SK_WORDS]) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_skeleton: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_skeleton: no such member");
+  return chs_sk_look(b->m[(size_t)member], b->stream, &b->dt, &b->sk, threshold, side, max_subiters, out, "chs_batch_skeleton");
+}
+
+extern "C" int chs_batch_skeleton_hist(chs_batch h, int32_t nbins, int64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_skeleton_hist: null handle");
+  return chs_sk_hist(b->sk, b->m[0]->hc.device, b->stream, nbins, out, "chs_batch_skeleton_hist");
+}
+
+extern "C" int chs_batch_skeleton_plane(chs_batch h, uint64_t* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_skeleton_plane: null handle");
+  return chs_sk_plane(b->sk, b->m[0]->hc.device, b->stream, out, "chs_batch_skeleton_plane");
+}
+
+extern "C" int chs_batch_skeleton_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_sk_last_ms(b, b ? b->sk : nullptr, ms, "chs_batch_skeleton");
+}
+
+extern "C" int chs_batch_skeleton_thin_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_sk_thin_ms(b, b ? b->sk : nullptr, ms, "chs_batch_skeleton");
 }

@@ -319,6 +319,7 @@ struct Engine {
   void* tr = nullptr;          // droplet tracking: the frame, hash table, rows, events (chs_track.hip), at the first track look
   void* th = nullptr;          // local thickness: map, centre list, histogram, result, events (chs_thickness.hip), at the first look
   void* geo = nullptr;         // geodesic look: map, tile flags, histogram, profile, result, events (chs_geodesic.hip), at the first look
+  void* sk = nullptr;          // skeleton look: two bit planes, histogram, counters, result, events (chs_skeleton.hip), at the first look
 };
 
 void chs_set_error(const std::string& s);
@@ -524,6 +525,21 @@ int chs_th_map(void* buf, int device, hipStream_t s, int32_t* out, const char* w
 int chs_th_last_ms(const void* h, const void* buf, double* ms, const char* what);
 void chs_th_free(void** buf);
 void chs_th_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- skeleton look (chs_skeleton.hip) -------------------------------------------
+// The skeleton of a phase of E's field thresholded at `threshold` on stream `s`: a distance look
+// with the buffer set *dtbuf first (it stays that look's snapshot), then the bit plane of D2 > 0, its thinning to the fixed
+// point and the statistics with the buffer set *buf, both allocated here at the first look: out[CHS_SK_WORDS].
+// max_subiters: 0 for chs_skeleton_subiters_default(N); a look that needs more returns CHS_ELIMIT and leaves no skeleton
+// result.  Histogram and packed plane of the last look of a buffer set: chs_sk_hist, chs_sk_plane.
+int chs_sk_look(Engine* E, hipStream_t s, void** dtbuf, void** buf, double threshold, int32_t side, int64_t max_subiters,
+                int64_t* out, const char* who);
+int chs_sk_hist(void* buf, int device, hipStream_t s, int32_t nbins, int64_t* out, const char* who);
+int chs_sk_plane(void* buf, int device, hipStream_t s, uint64_t* out, const char* who);
+int chs_sk_last_ms(const void* h, const void* buf, double* ms, const char* what);
+int chs_sk_thin_ms(const void* h, const void* buf, double* ms, const char* what);   // the sub-iterations alone
+void chs_sk_free(void** buf);
+void chs_sk_forget(void* buf);   // the buffers stay, the last look goes
 
 // ---- chord lengths (chs_chords.hip) -------------------------------------------
 // The chord lengths of both phases of E's field thresholded at `threshold`, along rows and columns (DESIGN.md section

@@ -69,13 +69,7 @@ __host__ __device__ inline DtSummary dt_add(const DtSummary& x, const DtSummary&
   return s;
 }
 
-// k with k^2 <= v < (k+1)^2 for 0 <= v <= 2^30: the float root is off by one at most, two integer comparisons settle it
-__host__ __device__ inline int dt_isqrt(int v) {
-  int k = (int)sqrtf((float)v);
-  k -= (k * k > v) ? 1 : 0;
-  k += ((k + 1) * (k + 1) <= v) ? 1 : 0;
-  return k;
-}
+// (dt_isqrt, the radius bin: chs_look.h)
 
 // ---- phase 1a --------------------------------------------------------------------------------------------------------
 // grid (column strips, bands).  V: pixels per load (16 bytes where N is a multiple of V, else 1); a thread owns the V

@@ -38,6 +38,15 @@ __device__ __forceinline__ void chs_load(const T CHS_GLOBAL* src, T (&x)[V]) {
   }
 }
 
+// The radius bin of the distance look (chs_distance.hip) and of the looks that bin its D2 (chs_skeleton.hip):
+// k with k^2 <= v < (k+1)^2 for 0 <= v <= 2^30: the float root is off by one at most, two integer comparisons settle it
+__host__ __device__ inline int dt_isqrt(int v) {
+  int k = (int)sqrtf((float)v);
+  k -= (k * k > v) ? 1 : 0;
+  k += ((k + 1) * (k + 1) <= v) ? 1 : 0;
+  return k;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 // What the buffer set of every look begins with.
 struct LookBase {

@@ -14,7 +14,8 @@ next call continues from (solver.py:158).
 """
 import numpy as np
 
-from . import _lib, chords, components, composition, contour, distance, geodesic, morphology, mport, shapes, spectrum, thickness, tracking, two_point
+from . import (_lib, chords, components, composition, contour, distance, geodesic, morphology, mport, shapes, skeleton, spectrum,
+               thickness, tracking, two_point)
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -239,6 +240,22 @@ class Solver:
         eng = self._look_engine()
         words, hi, pr, g = eng.geodesic_look(t, conn, code, src, hist, profile, map, max_rounds)
         return geodesic.Geodesic(words, self.params.N, t, conn, code, src, hist=hi, profile=pr, g=g, delx=self.solution.delx)
+
+    def skeleton(self, threshold=None, side='below', hist=True, map=False, max_subiters=None):
+        """The skeleton look at a phase of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): the medial network of the phase by a topology-preserving parallel thinning on the device --
+        its dead ends, links, branch points and crossings, the length of network per area, its coordination and the
+        half-widths along it, the narrowest neck among them -- a self-contained `skeleton.Skeleton` from a look on the
+        device between two calls, which the run does not notice.  ``side`` as for `distance`; the histogram of the widths
+        and the packed plane (``map=True``; N*N/8 bytes, `Skeleton.mask()` unpacks it) are fetched in this call when asked
+        for.  ``max_subiters`` (None: ``_lib.skeleton_subiters_default(N)``) bounds the sub-iterations, a kernel launch
+        each: a field that needs more raises `_lib.SkeletonLimitError` with ``subiters`` and ``limit``.  Needs a field:
+        prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        code = skeleton.side_code(side)
+        eng = self._look_engine()
+        words, hi, plane = eng.skeleton_look(t, code, hist, map, max_subiters)
+        return skeleton.Skeleton(words, self.params.N, t, code, hist=hi, plane=plane, delx=self.solution.delx)
 
     def chords(self, threshold=None, hist=True):
         """The chord lengths (linear intercepts) of the field the device holds, thresholded at `threshold` (None:

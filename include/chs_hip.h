@@ -37,7 +37,7 @@ extern "C" {
 #define CHS_ESTATE (-4)   /* call order violated (e.g. step before prepare:
                              the assert at chsimpy/solver.py:139)                */
 #define CHS_ECHECK (-5)   /* a self-check of a device result failed (chs_components) */
-/* -6: a look would cost more than its caller allows (chs_thickness: WORK > max_work; chs_geodesic: max_rounds).  Written relative to CHS_ECHECK:
+/* -6: a look would cost more than its caller allows (chs_thickness: WORK > max_work; chs_geodesic: max_rounds; chs_skeleton: max_subiters).  Written relative to CHS_ECHECK:
  * tests/test_components_host.py reads the literal codes above and holds CHS_ECHECK to be the last of them. */
 #define CHS_ELIMIT (CHS_ECHECK - 1)
 
@@ -553,6 +553,84 @@ int chs_geodesic_map(chs_handle h, int32_t* out);                   /* [N][N] G 
 int chs_geodesic_last_ms(chs_handle h, double* ms);
 int chs_geodesic_relax_ms(chs_handle h, double* ms);
 
+/* ---- Skeleton of a phase of the thresholded field: its medial network ----
+ * Foreground X and squared distance D2: exactly those of chs_distance -- `side`, the NaN and threshold conventions,
+ * CHS_DT_INF.  A skeleton look is a distance look first, on the handle's distance buffers: afterwards chs_distance_hist /
+ * _map return that look's D2.  The mask that is thinned is D2 > 0.  For the thinning everything outside the box is
+ * background; the foreground is 8-connected and the background 4-connected; there is no connectivity argument.
+ * Neighbourhood: the neighbours of a pixel are x0 .. x7 clockwise from north: N, NE, E, SE, S, SW, W, NW (north is row
+ * i - 1, east column j + 1).  B = sum of x_k.  The Yokoi 8-connectivity number is
+ *     Y = sum over k in {0, 2, 4, 6} of  (not x_k) and (x_{k+1} or x_{k+2}),   indices mod 8.
+ * Sub-iteration: one of direction d deletes, synchronously (all pixels read, then all deletions), every foreground pixel
+ * whose neighbour in direction d is background, with Y == 1 and B >= 2.  Sub-iteration i = 1, 2, ... has direction
+ * (N, S, E, W)[(i - 1) mod 4].  This is Rosenfeld's directional deletion of simple border points that are no end points:
+ * it keeps the 8-components of the phase and the 4-components of the background.
+ * Skeleton: the plane after the first four consecutive sub-iterations that delete nothing; SUBITERS is the index of the
+ * last sub-iteration that deleted a pixel, 0 if none did.  Every sub-iteration is a function of the plane before it, so
+ * plane and SUBITERS are unique: the device returns the bits of the numpy model (chsimpy_amd/skeleton.py).
+ * Result words: CHS_SK_WORDS int64 words at the indices below; B and Y are taken in the skeleton:
+ *   FG          foreground pixels
+ *   PIXELS      skeleton pixels
+ *   ISOLATED    skeleton pixels with B = 0
+ *   ENDS        skeleton pixels with B = 1
+ *   Y1 .. Y4    skeleton pixels by Yokoi number: edge, link, branch, crossing (Y = 0 is the rest)
+ *   AXIAL       pairs of skeleton pixels that are 4-adjacent
+ *   DIAGONAL    pairs of skeleton pixels that are diagonally adjacent
+ *   SUMD2       the sum of D2 over the skeleton pixels with D2 < CHS_DT_INF
+ *   D2MAX       the largest such D2, 0 if there is none
+ *   D2MIN_LINK  the smallest D2 over the Y == 2 pixels, the narrowest neck; 0 if there is none (CHS_DT_INF where the grid
+ *               has no background pixel)
+ *   NINF        skeleton pixels with D2 == CHS_DT_INF
+ *   EULER8      the Euler number of the skeleton at 8-connectivity, from 2 x 2 pattern counts:
+ *               PIXELS - AXIAL - DIAGONAL + (windows of exactly three pixels) + 3 (full windows); it equals that of the
+ *               phase, (Q1 - Q3 - 2 QD) / 4 of chs_morphology
+ *   SUBITERS    as above
+ *   LIMIT       the limit of this look
+ * Histogram: hist[k], int64, length chs_distance_bins(N): the skeleton pixels with isqrt(D2) == k, the width distribution
+ * along the network; CHS_DT_INF pixels are in no bin.
+ * Plane: N x ceil(N / 64) uint64 words; bit j of word w of a row is column 64 w + j; the bits at or beyond N are zero.
+ * The limit.  max_subiters = 0 means chs_skeleton_subiters_default(N) = 4 N + 64: twice what a full grid needs (2 N or 2 N + 1
+ * with its four quiet sub-iterations) plus slack -- a searched bound, not a proven one; 0 for
+ * N < 1.  A negative max_subiters or one above 16 defaults is CHS_EINVAL.  A look whose SUBITERS + 4 exceeds the limit --
+ * the limit used up while a pixel was deleted in its last four sub-iterations -- returns CHS_ELIMIT, chs_last_error naming
+ * both numbers: that look has no skeleton result (its fetches return CHS_ESTATE), the distance look of the same call is
+ * complete and can be fetched; of `out` SUBITERS (the last deleting sub-iteration seen) and LIMIT are set and every other
+ * word is 0.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it reads the field
+ * alone (through the distance look) and writes buffers of its own, so the run does not notice it; everything is integer,
+ * so two looks return the same bits.  Histogram and plane of the last look stay available until the next look.  The look
+ * checks itself: EULER8 equals the Euler number of the phase, PIXELS <= FG, FG equals the distance look's, PIXELS ==
+ * ISOLATED + ENDS + (pixels with B >= 2), SUBITERS + 4 <= the sub-iterations issued; a violation is CHS_ECHECK.
+ * CHS_EINVAL (the last look undisturbed) for a null argument, a threshold that is not finite, a side other than 0 or 1,
+ * max_subiters out of range, or nbins != chs_distance_bins(N) (the message gives the expected value); CHS_ESTATE for
+ * _hist / _plane / _last_ms / _thin_ms without a look. */
+#define CHS_SK_WORDS 17
+#define CHS_SK_FG 0
+#define CHS_SK_PIXELS 1
+#define CHS_SK_ISOLATED 2
+#define CHS_SK_ENDS 3
+#define CHS_SK_Y1 4
+#define CHS_SK_Y2 5
+#define CHS_SK_Y3 6
+#define CHS_SK_Y4 7
+#define CHS_SK_AXIAL 8
+#define CHS_SK_DIAGONAL 9
+#define CHS_SK_SUMD2 10
+#define CHS_SK_D2MAX 11
+#define CHS_SK_D2MIN_LINK 12
+#define CHS_SK_NINF 13
+#define CHS_SK_EULER8 14
+#define CHS_SK_SUBITERS 15
+#define CHS_SK_LIMIT 16
+int64_t chs_skeleton_subiters_default(int32_t N);   /* 4 N + 64; 0 for N < 1 */
+int chs_skeleton(chs_handle h, double threshold, int32_t side, int64_t max_subiters, int64_t out[CHS_SK_WORDS]);
+int chs_skeleton_hist(chs_handle h, int32_t nbins, int64_t* out);   /* [nbins] of the last look */
+int chs_skeleton_plane(chs_handle h, uint64_t* out);                /* [N][ceil(N / 64)] of the last look */
+/* Device time (ms, HIP events) of the handle's last look, the distance look inside included; _thin_ms: of its
+ * sub-iterations alone, the host's looks at the counter between them included. */
+int chs_skeleton_last_ms(chs_handle h, double* ms);
+int chs_skeleton_thin_ms(chs_handle h, double* ms);
+
 /* ---- Chord lengths (linear intercepts) of both phases, along rows and columns ----
  * For the N x N field U and a finite threshold t:
  * Phase 0 is the foreground of chs_components with CHS_CC_BELOW: X[i][j] = ((double)U[i][j] < t); a NaN pixel and a
@@ -1053,6 +1131,15 @@ int chs_batch_geodesic_hist(chs_batch b, int32_t nbins, int64_t* out);
 int chs_batch_geodesic_profile(chs_batch b, int64_t* out);
 int chs_batch_geodesic_map(chs_batch b, int32_t* out);
 int chs_batch_geodesic_last_ms(chs_batch b, double* ms);
+/* chs_skeleton of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of distance buffers and one
+ * set of skeleton buffers for the batch, so histogram, plane and times are those of the batch's last look, whichever
+ * member it was (and chs_batch_distance_hist / _map those of the distance look inside).  Words, histogram and plane are
+ * those of the member's single handle on the same field.  The members' states, fields and records stay untouched. */
+int chs_batch_skeleton(chs_batch b, int32_t member, double threshold, int32_t side, int64_t max_subiters, int64_t out[CHS_SK_WORDS]);
+int chs_batch_skeleton_hist(chs_batch b, int32_t nbins, int64_t* out);
+int chs_batch_skeleton_plane(chs_batch b, uint64_t* out);
+int chs_batch_skeleton_last_ms(chs_batch b, double* ms);
+int chs_batch_skeleton_thin_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }
