@@ -47,6 +47,9 @@ CHS_GEO_WORDS = 16            # int64 words of chs_geodesic (chsimpy_amd/geodesi
 CHS_GEO_ROUNDS, CHS_GEO_LIMIT = 14, 15
 CHS_SK_WORDS = 17             # int64 words of chs_skeleton (chsimpy_amd/skeleton.py names them)
 CHS_SK_SUBITERS, CHS_SK_LIMIT = 15, 16
+CHS_TRN_WORDS = 10            # int64 words of chs_transport (chsimpy_amd/transport.py names them)
+CHS_TRN_VALS = 8              # doubles of chs_transport
+CHS_TRN_CC_COUNT, CHS_TRN_ITERS, CHS_TRN_LIMIT = 2, 7, 9
 
 STOP_NAMES = {CHS_STOP_NONE: 'None', CHS_STOP_ENERGY: 'energy', CHS_STOP_TIME_LIMIT: 'time-limit'}
 STOP_CODES = {v: k for k, v in STOP_NAMES.items()}
@@ -88,6 +91,9 @@ SYMBOLS = (
     'chs_skeleton_subiters_default', 'chs_skeleton', 'chs_skeleton_hist', 'chs_skeleton_plane', 'chs_skeleton_last_ms',
     'chs_skeleton_thin_ms', 'chs_batch_skeleton', 'chs_batch_skeleton_hist', 'chs_batch_skeleton_plane',
     'chs_batch_skeleton_last_ms', 'chs_batch_skeleton_thin_ms',
+    'chs_transport_iters_default', 'chs_transport', 'chs_transport_profile', 'chs_transport_map', 'chs_transport_last_ms',
+    'chs_transport_solve_ms', 'chs_batch_transport', 'chs_batch_transport_profile', 'chs_batch_transport_map',
+    'chs_batch_transport_last_ms', 'chs_batch_transport_solve_ms',
 )
 
 # the N a batch takes (include/chs_hip.h: chs_batch_create): the fast engine's batch at BATCH_SIZES, the chirp engine's
@@ -142,6 +148,16 @@ class GeodesicLimitError(EngineError):
     def __init__(self, message, rounds, limit):
         super().__init__(message)
         self.rounds, self.limit = int(rounds), int(limit)
+
+
+class TransportLimitError(EngineError):
+    """A transport look that ran out of iterations (CHS_ELIMIT): the solve was not accepted after ``iters`` conjugate-gradient
+    iterations, the caller allowed ``limit``.  There is no transport result; the components look of the same call is
+    complete."""
+
+    def __init__(self, message, iters, limit):
+        super().__init__(message)
+        self.iters, self.limit = int(iters), int(limit)
 
 
 _lib = None
@@ -332,6 +348,18 @@ def load():
     lib.chs_batch_geodesic_profile.argtypes = [vp, i64p]
     lib.chs_batch_geodesic_map.argtypes = [vp, i32p]
     lib.chs_batch_geodesic_last_ms.argtypes = [vp, dp]
+    lib.chs_transport_iters_default.argtypes = [C.c_int32]
+    lib.chs_transport_iters_default.restype = C.c_int64
+    lib.chs_transport.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int64, i64p, dp]
+    lib.chs_transport_profile.argtypes = [vp, dp]
+    lib.chs_transport_map.argtypes = [vp, dp]
+    lib.chs_transport_last_ms.argtypes = [vp, dp]
+    lib.chs_transport_solve_ms.argtypes = [vp, dp]
+    lib.chs_batch_transport.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int64, i64p, dp]
+    lib.chs_batch_transport_profile.argtypes = [vp, dp]
+    lib.chs_batch_transport_map.argtypes = [vp, dp]
+    lib.chs_batch_transport_last_ms.argtypes = [vp, dp]
+    lib.chs_batch_transport_solve_ms.argtypes = [vp, dp]
     lib.chs_skeleton_subiters_default.argtypes = [C.c_int32]
     lib.chs_skeleton_subiters_default.restype = C.c_int64
     lib.chs_skeleton.argtypes = [vp, C.c_double, C.c_int32, C.c_int64, i64p]
@@ -413,6 +441,11 @@ def geodesic_bins(N):
 def skeleton_subiters_default(N):
     """The default limit of the sub-iterations of chs_skeleton at grid size N (chs_skeleton_subiters_default): 4 N + 64."""
     return int(load().chs_skeleton_subiters_default(int(N)))
+
+
+def transport_iters_default(N):
+    """The default iteration limit of chs_transport at grid size N (chs_transport_iters_default): 48 N + 64."""
+    return int(load().chs_transport_iters_default(int(N)))
 
 
 def geodesic_rounds_default(N):
@@ -740,6 +773,49 @@ class _Looks:
     def skeleton_thin_ms(self):
         """Device time (ms) of the sub-iterations of the last skeleton look."""
         return self._last_ms(self._prefix + 'skeleton_thin_ms')
+
+    def _transport(self, lead, threshold, side, source, tol, max_iters):
+        words = np.empty(CHS_TRN_WORDS, dtype=np.int64)
+        vals = np.empty(CHS_TRN_VALS, dtype=np.float64)
+        limit = 0 if max_iters is None else int(max_iters)
+        what = self._prefix + 'transport'
+        rc = getattr(self.lib, what)(self._h, *lead, float(threshold), int(side), int(source), float(tol), limit, _i64ptr(words),
+                                     _dptr(vals))
+        if rc == CHS_ELIMIT:
+            msg = self.lib.chs_last_error().decode(errors='replace')
+            raise TransportLimitError(f"{what} refused ({rc}): {msg}", words[CHS_TRN_ITERS], words[CHS_TRN_LIMIT])
+        self._check(rc, what)
+        self._cc_count = int(words[CHS_TRN_CC_COUNT])      # (a transport look is a components look too)
+        return words, vals
+
+    def transport_profile(self):
+        """float64 [N + 1][3] of the last transport look: cut[k], the sum of c and the active pixels at depth k."""
+        out = np.empty((self.N + 1, 3), dtype=np.float64)
+        self._look_call('transport_profile', _dptr(out))
+        return out
+
+    def transport_map(self):
+        """float64 [N][N] of the last transport look: c, -1 on the background, -2 on foreground that is not active."""
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._look_call('transport_map', _dptr(out))
+        return out
+
+    def _transport_look(self, lead, threshold, side, source, tol, profile, map, max_iters):
+        """(words, vals, profile or None, map or None) of one transport look."""
+        words, vals = self._transport(lead, threshold, side, source, tol, max_iters)
+        return words, vals, self.transport_profile() if profile else None, self.transport_map() if map else None
+
+    def transport_ms(self):
+        """Device time (ms) of the last transport look, the components look inside included."""
+        return self._last_ms(self._prefix + 'transport_last_ms')
+
+    def transport_solve_ms(self):
+        """Device time (ms) of the iterations and closing sweeps of the last transport look."""
+        return self._last_ms(self._prefix + 'transport_solve_ms')
+
+    def transport_iters_default(self):
+        """The default iteration limit of a transport look at this grid size."""
+        return int(self.lib.chs_transport_iters_default(self.N))
 
     def _chords(self, lead, threshold):
         out = np.empty(CHS_CH_WORDS, dtype=np.int64)
@@ -1098,6 +1174,16 @@ class Engine(_Looks):
     def geodesic_look(self, threshold, connectivity, side, source, hist=True, profile=True, map=False, max_rounds=None):
         return self._geodesic_look((), threshold, connectivity, side, source, hist, profile, map, max_rounds)
 
+    def transport(self, threshold, side=CHS_CC_BELOW, source=0, tol=1e-6, max_iters=None):
+        """(words, vals) of the transport look at the field the device holds (chs_transport; chsimpy_amd/transport.py
+        names them).  Profile and map of this look: `transport_profile`, `transport_map`; it is a components look as
+        well.  A solve that is not accepted within `max_iters` iterations (None: the default) raises
+        `TransportLimitError`."""
+        return self._transport((), threshold, side, source, tol, max_iters)
+
+    def transport_look(self, threshold, side, source, tol=1e-6, profile=True, map=False, max_iters=None):
+        return self._transport_look((), threshold, side, source, tol, profile, map, max_iters)
+
     def geodesic_relax_ms(self):
         """Device time (ms) of the relaxation rounds of the last geodesic look."""
         return self._last_ms('chs_geodesic_relax_ms')
@@ -1348,6 +1434,13 @@ class Batch(_Looks):
     def geodesic(self, member, threshold, connectivity=8, side=CHS_CC_BELOW, source=0, max_rounds=None):
         """`Engine.geodesic` of one member (chs_batch_geodesic)."""
         return self._geodesic((int(member),), threshold, connectivity, side, source, max_rounds)
+
+    def transport(self, member, threshold, side=CHS_CC_BELOW, source=0, tol=1e-6, max_iters=None):
+        """`Engine.transport` of one member (chs_batch_transport)."""
+        return self._transport((int(member),), threshold, side, source, tol, max_iters)
+
+    def transport_look(self, member, threshold, side, source, tol=1e-6, profile=True, map=False, max_iters=None):
+        return self._transport_look((int(member),), threshold, side, source, tol, profile, map, max_iters)
 
     def geodesic_look(self, member, threshold, connectivity, side, source, hist=True, profile=True, map=False, max_rounds=None):
         return self._geodesic_look((int(member),), threshold, connectivity, side, source, hist, profile, map, max_rounds)

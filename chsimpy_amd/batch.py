@@ -129,7 +129,8 @@ class _Member:
     _LOOKS = ('components', 'components_look', 'distance', 'distance_look', 'chords', 'chords_look', 'composition',
               'composition_look', 'composition_select', 'two_point', 'two_point_look', 'contour', 'contour_look', 'shapes',
               'shapes_look', 'track', 'track_look', 'track_reset', 'thickness', 'thickness_look',
-              'geodesic', 'geodesic_look', 'skeleton', 'skeleton_look')
+              'geodesic', 'geodesic_look', 'skeleton', 'skeleton_look',
+              'transport', 'transport_look')
 
     def __getattr__(self, name):
         """A look of the member by the signature of `Engine`: the batch's, with the member in front."""
@@ -320,6 +321,10 @@ class BatchSolver:
     def skeleton(self, member=None, threshold=None, side='below', hist=True, map=False, max_subiters=None):
         """The members' skeleton looks (`Solver.skeleton`), a `skeleton.Skeleton` each: _member_by_member."""
         return self._member_by_member('skeleton', member, threshold, side, hist, map, max_subiters)
+
+    def transport(self, member=None, threshold=None, side='below', source='top', tol=1e-6, profile=True, map=False, max_iters=None):
+        """The members' transport looks (`Solver.transport`), a `transport.Transport` each: _member_by_member."""
+        return self._member_by_member('transport', member, threshold, side, source, tol, profile, map, max_iters)
 
     def chords(self, member=None, threshold=None, hist=True):
         """The members' chord lengths (`Solver.chords`), a `chords.Chords` each: _member_by_member."""

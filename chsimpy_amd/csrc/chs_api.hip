@@ -98,6 +98,7 @@ static void free_engine(Engine* E) {
   chs_th_free(&E->th);
   chs_geo_free(&E->geo);
   chs_sk_free(&E->sk);
+  chs_trn_free(&E->trn);
   hipFree(E->dU); hipFree(E->dMU); hipFree(E->dT2);
   hipFree(E->dT1); hipFree(E->dHat);
   if (E->dHat2) hipFree(E->dHat2);
@@ -210,6 +211,7 @@ static int rearm(Engine* E, const chs_consts* c) {
   chs_th_forget(E->th);
   chs_geo_forget(E->geo);
   chs_sk_forget(E->sk);
+  chs_trn_forget(E->trn);
   read_env_hooks(E);
   if (E->engine == CHS_ENGINE_FAST) return chs_fast_rearm(E);
   return CHS_OK;

@@ -174,6 +174,7 @@ struct Batch {
   void* th = nullptr;            // chs_batch_thickness: the batch's one set of buffers (chs_thickness.hip), at the first look
   void* geo = nullptr;           // chs_batch_geodesic: the batch's one set of buffers (chs_geodesic.hip), at the first look
   void* sk = nullptr;            // chs_batch_skeleton: the batch's one set of buffers (chs_skeleton.hip), at the first look
+  void* trn = nullptr;           // chs_batch_transport: the batch's one set of buffers (chs_transport.hip), at the first look
 };
 
 bool batch_n_ok(int N) { return N == 128 || N == 256 || N == 512 || N == 1024 || N == 2048; }
@@ -202,6 +203,7 @@ void batch_free(Batch* b) {
   chs_th_free(&b->th);
   chs_geo_free(&b->geo);
   chs_sk_free(&b->sk);
+  chs_trn_free(&b->trn);
   if (b->dMem) hipFree(b->dMem);
   if (b->dNat) hipFree(b->dNat);
   if (b->dSeat) hipFree(b->dSeat);
@@ -1084,4 +1086,37 @@ extern "C" int chs_batch_skeleton_last_ms(chs_batch h, double* ms) {
 extern "C" int chs_batch_skeleton_thin_ms(chs_batch h, double* ms) {
   Batch* b = as_batch(h);
   return chs_sk_thin_ms(b, b ? b->sk : nullptr, ms, "chs_batch_skeleton");
+}
+
+// The transport look at one member: the single handle's look on the batch's stream, with the batch's one set of component
+// buffers and one set of transport buffers.
+extern "C" int chs_batch_transport(chs_batch h, int32_t member, double threshold, int32_t side, int32_t source, double tol,
+                                   int64_t max_iters, int64_t words[CHS_TRN_WORDS], double vals[CHS_TRN_VALS]) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_transport: null handle");
+  if (member < 0 || member >= b->B) return bad("chs_batch_transport: no such member");
+  return chs_trn_look(b->m[(size_t)member], b->stream, &b->cc, &b->trn, threshold, side, source, tol, max_iters, words, vals,
+                      "chs_batch_transport");
+}
+
+extern "C" int chs_batch_transport_profile(chs_batch h, double* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_transport_profile: null handle");
+  return chs_trn_profile(b->trn, b->m[0]->hc.device, b->stream, out, "chs_batch_transport_profile");
+}
+
+extern "C" int chs_batch_transport_map(chs_batch h, double* out) {
+  Batch* b = as_batch(h);
+  if (!b) return bad("chs_batch_transport_map: null handle");
+  return chs_trn_map(b->trn, b->m[0]->hc.device, b->stream, out, "chs_batch_transport_map");
+}
+
+extern "C" int chs_batch_transport_last_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_trn_last_ms(b, b ? b->trn : nullptr, ms, "chs_batch_transport");
+}
+
+extern "C" int chs_batch_transport_solve_ms(chs_batch h, double* ms) {
+  Batch* b = as_batch(h);
+  return chs_trn_solve_ms(b, b ? b->trn : nullptr, ms, "chs_batch_transport");
 }

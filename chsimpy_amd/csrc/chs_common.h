@@ -320,6 +320,7 @@ struct Engine {
   void* th = nullptr;          // local thickness: map, centre list, histogram, result, events (chs_thickness.hip), at the first look
   void* geo = nullptr;         // geodesic look: map, tile flags, histogram, profile, result, events (chs_geodesic.hip), at the first look
   void* sk = nullptr;          // skeleton look: two bit planes, histogram, counters, result, events (chs_skeleton.hip), at the first look
+  void* trn = nullptr;         // transport look: pixel bytes, the vectors of the iteration, tile list, profile, result, events (chs_transport.hip), at the first look
 };
 
 void chs_set_error(const std::string& s);
@@ -540,6 +541,22 @@ int chs_sk_last_ms(const void* h, const void* buf, double* ms, const char* what)
 int chs_sk_thin_ms(const void* h, const void* buf, double* ms, const char* what);   // the sub-iterations alone
 void chs_sk_free(void** buf);
 void chs_sk_forget(void* buf);   // the buffers stay, the last look goes
+
+// ---- transport look (chs_transport.hip) -----------------------------------------
+// The steady diffusion problem through the spanning components of a phase of E's field thresholded at `threshold`, from
+// the wall `source` to the opposite one on stream `s`: a components look at connectivity 4 with the
+// buffer set *ccbuf first (it stays that look's snapshot), then setup, conjugate-gradient iterations and closing sweep with
+// the buffer set *buf, both allocated here at the first look: words[CHS_TRN_WORDS], vals[CHS_TRN_VALS].  max_iters: 0 for
+// chs_transport_iters_default(N); a solve that is not accepted by then returns CHS_ELIMIT and leaves no transport result.
+// Profile and map of the last look of a buffer set: chs_trn_profile, chs_trn_map.
+int chs_trn_look(Engine* E, hipStream_t s, void** ccbuf, void** buf, double threshold, int32_t side, int32_t source, double tol,
+                 int64_t max_iters, int64_t* words, double* vals, const char* who);
+int chs_trn_profile(void* buf, int device, hipStream_t s, double* out, const char* who);
+int chs_trn_map(void* buf, int device, hipStream_t s, double* out, const char* who);
+int chs_trn_last_ms(const void* h, const void* buf, double* ms, const char* what);
+int chs_trn_solve_ms(const void* h, const void* buf, double* ms, const char* what);   // iterations and closing sweeps alone
+void chs_trn_free(void** buf);
+void chs_trn_forget(void* buf);   // the buffers stay, the last look goes
 
 // ---- chord lengths (chs_chords.hip) -------------------------------------------
 // The chord lengths of both phases of E's field thresholded at `threshold`, along rows and columns (DESIGN.md section

@@ -15,7 +15,7 @@ next call continues from (solver.py:158).
 import numpy as np
 
 from . import (_lib, chords, components, composition, contour, distance, geodesic, morphology, mport, shapes, skeleton, spectrum,
-               thickness, tracking, two_point)
+               thickness, tracking, transport, two_point)
 from .solution import Solution, _fingerprint
 from .timedata import TimeData
 
@@ -256,6 +256,23 @@ class Solver:
         eng = self._look_engine()
         words, hi, plane = eng.skeleton_look(t, code, hist, map, max_subiters)
         return skeleton.Skeleton(words, self.params.N, t, code, hist=hi, plane=plane, delx=self.solution.delx)
+
+    def transport(self, threshold=None, side='below', source='top', tol=1e-6, profile=True, map=False, max_iters=None):
+        """The transport look at a phase of the field the device holds, thresholded at `threshold` (None:
+        ``params.threshold``): steady diffusion through the phase alone from the wall ``source`` ('top', 'bottom', 'left',
+        'right'), held at c = 1, to the opposite wall, held at c = 0, solved on the device by conjugate gradients in fp64
+        -- the effective diffusivity ``deff`` = D_eff / D_0 with its certified error bound, the formation factor and the
+        tortuosity factor eps / deff -- a self-contained `transport.Transport` from a look on the device between two
+        calls, which the run does not notice.  ``side`` as for `components` (the connectivity is 4); ``tol`` in [1e-12,
+        1e-2] is the relative accuracy of ``deff`` the look has to certify; the profile by depth and the N x N map of c
+        are fetched in this call when asked for (without ``map=True`` nothing N x N leaves the device).  ``max_iters``
+        (None: ``_lib.transport_iters_default(N)``) bounds the iterations: a solve that is not accepted by then raises
+        `_lib.TransportLimitError` with ``iters`` and ``limit``.  Needs a field: prepare() first."""
+        t = float(self.params.threshold if threshold is None else threshold)
+        code, src = components.side_code(side), transport.source_code(source)
+        eng = self._look_engine()
+        words, vals, pr, cm = eng.transport_look(t, code, src, tol, profile, map, max_iters)
+        return transport.Transport(words, vals, self.params.N, t, code, src, profile=pr, c=cm, delx=self.solution.delx)
 
     def chords(self, threshold=None, hist=True):
         """The chord lengths (linear intercepts) of the field the device holds, thresholded at `threshold` (None:

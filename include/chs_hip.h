@@ -631,6 +631,91 @@ int chs_skeleton_plane(chs_handle h, uint64_t* out);                /* [N][ceil(
 int chs_skeleton_last_ms(chs_handle h, double* ms);
 int chs_skeleton_thin_ms(chs_handle h, double* ms);
 
+/* ---- Transport look at a phase of the thresholded field: effective diffusivity ----
+ * Foreground and walls.  `threshold`, `side` (0 below, 1 above) and the NaN convention are those of chs_components at
+ * connectivity 4, with no wrap-around.  A transport look is a components look at connectivity 4 first, on the handle's
+ * component buffers: afterwards chs_components_table / _labels return that look.  `source` is 0 to 3 as in chs_geodesic
+ * (0 is row 0, 1 is row N-1, 2 is column 0, 3 is column N-1); the target is the opposite wall; the depth k of a pixel is
+ * its distance from the source wall along that axis.
+ * Active set.  The active pixels are those of the components whose bounding box touches both the source wall and the
+ * target wall.  Every other pixel carries no flux and takes no part in the solve; this also keeps the system non-singular.
+ * System.  One unknown c_p per active pixel.  Two 4-adjacent active pixels share a bond of conductance 1.  An active pixel
+ * on the source wall has a bond of conductance 2 to the wall face, which is held at c = 1 (the face is half a pixel away);
+ * an active pixel on the target wall has a bond of conductance 2 to the wall face, which is held at c = 0.  No flux passes
+ * through the other two walls or into pixels that are not active.  A c = b is the balance of every pixel: b_p = 2 on the
+ * source wall and 0 elsewhere; A is symmetric positive definite.
+ * Results.  F_in = sum over the source wall of 2 (1 - c_p); F_out = sum over the target wall of 2 c_p; cut[k], k = 0 .. N,
+ * is the flux through the face between depth k-1 and depth k, so cut[0] = F_in and cut[N] = F_out.  For the exact
+ * solution all cuts equal F*, and D_eff / D_0 = F* (the box is square and the difference of c is 1).  The formation factor
+ * is 1 / F*; with the porosity eps = FG / N^2 the tortuosity factor is eps / F*.
+ * Certificate.  With r = b - A c evaluated from the returned c the following hold exactly (maximum principle: the adjoint
+ * potentials lie in [0, 1]): |F_out - F*| <= |r|_1 and |F_in - F*| <= |r|_1; |cut[k] - F_out| = |sum over depth >= k of
+ * r_p| <= |r|_1.
+ * Acceptance.  A look succeeds only if RES1 <= tol min(F_in, F_out), RES1 being the 1-norm of the true residual,
+ * recomputed from the final c in a closing sweep; the recurrence residual of the iteration does not count.  `tol` is the
+ * relative accuracy of D_eff that the caller asks for, in [1e-12, 1e-2]; 1e-6 is what the Python side passes by default.
+ * The look checks this itself, and that every cut lies within RES1 of F_OUT up to the rounding of the sums; a
+ * failure is CHS_ECHECK.
+ * Words: CHS_TRN_WORDS int64 words at the indices below (CHS_TR_ is the tracking look's prefix):
+ *   FG, ACTIVE           foreground pixels, active pixels
+ *   CC_COUNT             components of the components look
+ *   CC_SPANNING          those of them whose bounding box touches both walls
+ *   SRC_PIXELS           active pixels on the source wall
+ *   TGT_PIXELS           active pixels on the target wall
+ *   BONDS                pairs of 4-adjacent active pixels
+ *   ITERS                conjugate-gradient iterations
+ *   CHECKS               closing sweeps, each a true residual
+ *   LIMIT                the iteration limit that applied
+ * Values: CHS_TRN_VALS doubles: F_IN, F_OUT, RES1, RESINF (the largest |r_p|), CUT_MIN, CUT_MAX (over the N + 1 cuts),
+ * CSUM (the sum of c over the active pixels), TOL.
+ * Profile: double [N+1][3], one row per face or depth k: cut[k], the sum of c at depth k, the active pixels at depth k;
+ * row N holds zeros in the last two columns.
+ * Map: double [N][N]: c on the active pixels, -1.0 on the background, -2.0 on foreground that is not active.
+ * The solve is in fp64 whatever the engine's element type; the field is read only through the components look.  Plain
+ * conjugate gradients without a preconditioner and without restarts, matrix-free on 64 x 64 tiles; every sum has a
+ * fixed order, so two looks at one field return the same bits in map, profile and values.
+ * No spanning component: ACTIVE == 0 is a good look; no iteration runs, ITERS = 0 and every value is 0 (TOL too): D_eff =
+ * 0 is the answer.
+ * The limit.  max_iters bounds the iterations: 0 means chs_transport_iters_default(N) = 48 N + 64, a searched bound
+ * (evolved fields near the percolation threshold needed up to 21 N; at N = 4096 that is tens of thousands of iterations and many
+ * seconds -- the look is meant for N <= 2048); a negative max_iters or one above 16 defaults is CHS_EINVAL.  A solve that is
+ * not accepted within the limit returns CHS_ELIMIT, chs_last_error naming the iterations and the limit: ITERS and LIMIT
+ * are filled and every other word and value is 0; there is no transport result (its fetches return CHS_ESTATE); the
+ * components look of the call is complete.
+ * A look works on any handle that holds a field (else CHS_ESTATE), between two chs_step_n calls too: it writes buffers of
+ * its own, so the run does not notice it.  The argument checks, in this order and before the last look is touched: a null
+ * argument, a threshold that is not finite, the side, the source, tol, max_iters (all CHS_EINVAL), then the field
+ * (CHS_ESTATE).  CHS_ESTATE for _profile / _map / _last_ms / _solve_ms without a look. */
+#define CHS_TRN_WORDS 10
+#define CHS_TRN_FG 0
+#define CHS_TRN_ACTIVE 1
+#define CHS_TRN_CC_COUNT 2
+#define CHS_TRN_CC_SPANNING 3
+#define CHS_TRN_SRC_PIXELS 4
+#define CHS_TRN_TGT_PIXELS 5
+#define CHS_TRN_BONDS 6
+#define CHS_TRN_ITERS 7
+#define CHS_TRN_CHECKS 8
+#define CHS_TRN_LIMIT 9
+#define CHS_TRN_VALS 8
+#define CHS_TRN_F_IN 0
+#define CHS_TRN_F_OUT 1
+#define CHS_TRN_RES1 2
+#define CHS_TRN_RESINF 3
+#define CHS_TRN_CUT_MIN 4
+#define CHS_TRN_CUT_MAX 5
+#define CHS_TRN_CSUM 6
+#define CHS_TRN_TOL 7
+int64_t chs_transport_iters_default(int32_t N);    /* 48 N + 64; 0 for N < 1 */
+int chs_transport(chs_handle h, double threshold, int32_t side, int32_t source, double tol, int64_t max_iters,
+                  int64_t words[CHS_TRN_WORDS], double vals[CHS_TRN_VALS]);
+int chs_transport_profile(chs_handle h, double* out);   /* [N + 1][3] of the last look */
+int chs_transport_map(chs_handle h, double* out);       /* [N][N] of the last look */
+/* Device time (ms, HIP events) of the handle's last look, the components look inside included; _solve_ms: of its
+ * iterations and closing sweeps alone, the host's looks at the scalars between them included. */
+int chs_transport_last_ms(chs_handle h, double* ms);
+int chs_transport_solve_ms(chs_handle h, double* ms);
+
 /* ---- Chord lengths (linear intercepts) of both phases, along rows and columns ----
  * For the N x N field U and a finite threshold t:
  * Phase 0 is the foreground of chs_components with CHS_CC_BELOW: X[i][j] = ((double)U[i][j] < t); a NaN pixel and a
@@ -1140,6 +1225,17 @@ int chs_batch_skeleton_hist(chs_batch b, int32_t nbins, int64_t* out);
 int chs_batch_skeleton_plane(chs_batch b, uint64_t* out);
 int chs_batch_skeleton_last_ms(chs_batch b, double* ms);
 int chs_batch_skeleton_thin_ms(chs_batch b, double* ms);
+/* chs_transport of member `member` (in [0, B), else CHS_EINVAL) on the batch's stream; one set of component buffers and
+ * one set of transport buffers for the batch, so profile, map and times are those of the batch's last look, whichever
+ * member it was (and chs_batch_components_table / _labels those of the components look inside).  Words, values, profile
+ * and map are those of the member's single handle on the same field.  The members' states, fields and records stay
+ * untouched. */
+int chs_batch_transport(chs_batch b, int32_t member, double threshold, int32_t side, int32_t source, double tol, int64_t max_iters,
+                        int64_t words[CHS_TRN_WORDS], double vals[CHS_TRN_VALS]);
+int chs_batch_transport_profile(chs_batch b, double* out);
+int chs_batch_transport_map(chs_batch b, double* out);
+int chs_batch_transport_last_ms(chs_batch b, double* ms);
+int chs_batch_transport_solve_ms(chs_batch b, double* ms);
 
 #ifdef __cplusplus
 }

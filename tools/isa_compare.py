@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 TUS = ['chs_fast_f64.hip', 'chs_fast_f32.hip', 'chs_batch.hip', 'chs_pointwise.hip', 'chs_direct.hip', 'chs_fast.hip', 'chs_api.hip',
        'chs_chirp.hip', 'chs_spectrum.hip', 'chs_morphology.hip', 'chs_components.hip', 'chs_distance.hip', 'chs_chords.hip',
        'chs_composition.hip', 'chs_two_point.hip', 'chs_contour.hip', 'chs_track.hip', 'chs_thickness.hip',
-       'chs_geodesic.hip', 'chs_skeleton.hip']
+       'chs_geodesic.hip', 'chs_skeleton.hip', 'chs_transport.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-Wno-unused-value', '-Wno-unused-result', '-Wno-pass-failed',
          '-DCHS_TEST_HOOKS=1']
 
